@@ -95,6 +95,32 @@ def test_bench_refuses_a_traffic_file_from_other_kernel_sources(tmp_path):
     assert "kernel_sources_sha256" in tool
 
 
+def test_bench_dump_outputs_writes_float32_samples(tmp_path):
+    """`bench.py --dump-outputs DIR`: loss, logits and every parameter / gradient as float32 .npy, whole up to
+    DUMP_SAMPLE entries, else the same crc32(name)-seeded positions on every run; frozen parameters have no grad file."""
+    import bench
+    torch.manual_seed(0)
+    big = torch.nn.Linear(bench.DUMP_SAMPLE, 2)            # weight: 2 x DUMP_SAMPLE entries -> sampled
+    head = torch.nn.Linear(3, 2, bias=False).requires_grad_(False)
+    big(torch.randn(5, bench.DUMP_SAMPLE)).sum().backward()
+    logits = torch.randn(5, 10, dtype=torch.bfloat16).requires_grad_()     # a captured step's static output keeps its grad_fn
+    loss = torch.tensor(1.5, requires_grad=True)
+    bench.dump_outputs(str(tmp_path / "a"), loss, logits, [("", big), ("head.", head)])
+    bench.dump_outputs(str(tmp_path / "b"), loss, logits, [("", big), ("head.", head)])
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["grad.bias.npy", "grad.weight.npy", "logits.npy", "loss.npy",
+                     "param.bias.npy", "param.head.weight.npy", "param.weight.npy"]
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float32 and np.array_equal(x, y), f
+    assert np.load(tmp_path / "a" / "loss.npy") == np.float32(1.5)
+    assert np.array_equal(np.load(tmp_path / "a" / "logits.npy"), logits.detach().float().numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "param.bias.npy"), big.bias.detach().numpy())
+    idx = bench._grad_sample_index("weight", big.weight.numel(), bench.DUMP_SAMPLE)
+    assert np.array_equal(np.load(tmp_path / "a" / "grad.weight.npy"), big.weight.grad.reshape(-1)[idx].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "param.head.weight.npy"), head.weight.reshape(-1).numpy())
+
+
 # ------------------------------------------------------------------ early stopping (utils_network.py:322-328) ---
 def _scripted_network(val_accs):
     """A Network over a tiny CPU module whose epochs return scripted validation accuracies."""

@@ -334,6 +334,24 @@ def test_attention_online_softmax_rescale_branch(ops):
     assert_close("attn.rescale", O, o_ref, 1.5e-2)
 
 
+@pytest.mark.parametrize("B,N,H,hd", [(16, 197, 12, 64), (8, 256, 4, 32), (8, 100, 6, 64), (4, 300, 2, 64)])
+def test_attention_fwd_is_deterministic(ops, B, N, H, hd):
+    """The same input gives the same bits on every launch.  (The whole-sequence kernel, N <= 256, once took the row maximum
+    of each full key block with inline asm reading the score MFMA's result registers without its wait states: O and lse
+    changed from launch to launch.)"""
+    qkv = dev(bf16_round(gen((B, N, 3 * H * hd), 4)), torch.bfloat16)
+    runs = []
+    for _ in range(8):
+        O = torch.empty((B, N, H * hd), device="cuda", dtype=torch.bfloat16)
+        lse = torch.empty(B * H * N, device="cuda")
+        ops.attn_fwd(qkv, O, lse, B, N, H, hd, hd ** -0.5)
+        runs.append((O, lse))
+    torch.cuda.synchronize()
+    for i, (O, lse) in enumerate(runs[1:], 1):
+        assert torch.equal(O, runs[0][0]), f"launch {i}: {int((O != runs[0][0]).sum())} outputs differ from launch 0"
+        assert torch.equal(lse, runs[0][1]), f"launch {i}: lse differs from launch 0"
+
+
 # ------------------------------------------------------------ elementwise ---
 @pytest.mark.parametrize("n", [4, 1000, 4099, 1 << 20])
 def test_cast(ops, n):

@@ -322,6 +322,36 @@ def test_deferred_folds_leave_every_gradient_bit_identical(monkeypatch):
         assert torch.equal(grads[0][n], grads[1][n]), n
 
 
+@pytest.mark.parametrize("compute,residual", [("bf16", "bf16"), ("bf16", "fp32"), ("fp32", "fp32")])
+def test_repeated_step_is_bit_identical(compute, residual):
+    """Forward + backward on unchanged weights and batch, three times: the same logits, loss and gradients to the bit (what
+    bench.py --dump-outputs compares between runs).  197 tokens at head size 64, the benchmarked sequence: six full 32-key
+    blocks in the attention besides the ragged last one."""
+    from oracle import vit_ref
+    from vit_torch_amd import CrossEntropyLoss, VisionTransformer
+    cfg = dict(img_size=224, patch_size=16, in_chans=3, embed_dim=128, depth=2, num_heads=2)
+    x, y = data(8, 3, 224, 10, seed=5)
+    x, y = x.cuda(), y.cuda()
+    ref = vit_ref.VisionTransformer(**cfg, apply_head=True)
+    ref.head = vit_ref.get_classifier_head(128, 10)
+    vit_ref.seeded_init_(ref, 1)
+    m = VisionTransformer(**cfg, apply_head=True, compute_dtype=compute, residual_dtype=residual)
+    m.head = vit_ref.get_classifier_head(128, 10)
+    m.load_state_dict(ref.state_dict())
+    m = m.cuda()
+    runs = []
+    for _ in range(3):
+        m.zero_grad()
+        out = m(x)
+        loss = CrossEntropyLoss()(out, y)
+        loss.backward()
+        runs.append((out.detach().clone(), loss.detach().clone(), {n: p.grad.clone() for n, p in m.named_parameters()}))
+    for i, (out, loss, grads) in enumerate(runs[1:], 1):
+        assert torch.equal(out, runs[0][0]) and torch.equal(loss, runs[0][1]), f"step {i}: logits / loss differ"
+        for n in grads:
+            assert torch.equal(grads[n], runs[0][2][n]), f"step {i}: gradient of {n} differs"
+
+
 # ------------------------------------------------------------- torch's accumulation contract ---
 @pytest.mark.parametrize("compute", ["fp32", "bf16"])
 def test_second_backward_accumulates(compute):

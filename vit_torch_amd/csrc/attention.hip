@@ -119,6 +119,12 @@ __device__ __forceinline__ float max3f(float a, float b, float c) {
   asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
 }
+// hipcc pads no hazard around an asm statement (it neither sees nor pads what is inside one): the v_max3_f32 of max16 read
+// the scores straight from the MFMA's result registers, so without the XDL-write -> VALU-read wait states in between
+// (12 for the 8-pass v_mfma_f32_32x32x16_bf16) they could read an accumulator the MFMA was still writing — a row maximum,
+// and with it O and lse, that changed from launch to launch on the same input.  This pad (16 states) is tied to `s`
+// ("+v"), so it is scheduled after the MFMA and before every reader of its result.
+__device__ __forceinline__ void mfma_result_pad(f32x16& s) { asm volatile("s_nop 15" : "+v"(s)); }
 __device__ __forceinline__ float max16(const f32x16& s) {
   const float t0 = max3f(s[0], s[1], s[2]), t1 = max3f(s[3], s[4], s[5]), t2 = max3f(s[6], s[7], s[8]);
   const float t3 = max3f(s[9], s[10], s[11]), t4 = max3f(s[12], s[13], s[14]);
@@ -407,6 +413,7 @@ __global__ __launch_bounds__(512) void attn_fwd_whole_kernel(const bf16* __restr
       for (int r = 0; r < 16; ++r)
         if (key0 + mfma32_row(r, h5) >= N) s[r] = -INFINITY;
     }
+    mfma_result_pad(s);                        // max16 is inline asm: the MFMA's wait states are ours to insert
     float tmax = max16(s);
     tmax = max3f(tmax, __shfl_xor(tmax, 32), tmax);
     const float m_new = fmaxf(m, tmax * scale_log2e);
