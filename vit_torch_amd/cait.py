@@ -21,9 +21,10 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import EPI_BIAS_GELU, EPI_DGELU, EPI_PATCH_POS, EPI_RESIDUAL, GEMM_AUTO, VitmiError
-from .packing import ParamPack
-from .vit import Mlp, PatchEmbed, _DT, _EngineFn, _head_layers, _trunc_normal_, dgelu_gemm_with_bias_grad, engine_gemm
+from ._lib import EPI_BIAS_GELU, EPI_DGELU, EPI_PATCH_POS, EPI_RESIDUAL, VitmiError
+from .engine import Engine, EngineModel, mlp_backward, mlp_forward
+from .head import head_backward, head_forward
+from .vit import Mlp, PatchEmbed, _DT, _trunc_normal_
 
 
 class ClassAttention(nn.Module):
@@ -78,7 +79,7 @@ def _ln_eps(norm_layer, default=1e-5):
     return kw.get("eps", default)
 
 
-class cait_models(nn.Module):
+class cait_models(EngineModel, nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4.0, qkv_bias=False, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0,
                  drop_path_rate=0.0, norm_layer=nn.LayerNorm, init_scale=1e-4, depth_token_only=2,
@@ -123,19 +124,8 @@ class cait_models(nn.Module):
                 nn.init.zeros_(m.bias)
         self._engine: Optional[CaitEngine] = None
 
-    def engine(self):
-        if self._engine is None or not self._engine.is_current():
-            self._engine = CaitEngine(self)
-        return self._engine
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise VitmiError("vit_torch_amd models run on an MI355X (HIP) device; got a CPU tensor "
-                             "and there is no CPU fallback")
-        eng = self.engine()
-        if torch.is_grad_enabled() and any(p.requires_grad for p in eng.pack.params):
-            return _EngineFn.apply(eng, x, *eng.pack.params)
-        return eng.forward(x, save=False)
+    def _new_engine(self):
+        return CaitEngine(self)
 
 
 VARIANTS = {   # name: (img, embed_dim, depth, heads, init_scale)  models/cait.py:255-480
@@ -162,52 +152,13 @@ def _ru8(n):
     return (n + 7) // 8 * 8
 
 
-class CaitEngine:
+class CaitEngine(Engine):
     """Forward / backward kernel sequence of cait_models."""
 
     def __init__(self, model: cait_models):
-        self.model = model
-        dev = model.pos_embed.device
-        if dev.type != "cuda":
-            raise VitmiError("move the model to the GPU before the first forward")
-        self.T, self.R = model.compute_dtype, model.residual_dtype
-        self.split3 = bool(getattr(model, "split3", False))
+        super().__init__(model)
         # talking-heads attention as one fused op where the shape allows (VITMI_TH_FUSED=0: the three-call form, for A/B)
         self.fused_th = os.environ.get("VITMI_TH_FUSED", "1") != "0"
-        if self.T == torch.float32 and self.R != torch.float32:
-            raise VitmiError("fp32 compute needs an fp32 residual stream")
-        self.head = _head_layers(model.head)
-        if self.head is None:
-            raise VitmiError("head must be Identity, Linear or Sequential(Linear[, GELU], ...)")
-        self.pack = ParamPack(list(model.named_parameters()), dev, shadow=self.T == torch.bfloat16)
-        self.saved = None
-        self.reducer = None
-        # small folds of a backward pass in one launch per flush (ops.FoldQueue; VITMI_DEFER_FOLDS=0: at once)
-        self.folds = ops.FoldQueue() if os.environ.get("VITMI_DEFER_FOLDS", "1") != "0" else None
-        self.profile = None
-        self.gemm_impl = GEMM_AUTO
-
-    def is_current(self):
-        m = self.model
-        return (self.pack.is_current() and m.compute_dtype == self.T and m.residual_dtype == self.R
-                and bool(getattr(m, "split3", False)) == self.split3
-                and len(self.pack.params) == sum(1 for _ in m.parameters()))
-
-    def _w(self, p):
-        return self.pack.w(p)
-
-    def _gemm(self, A, B, C, **k):
-        return engine_gemm(self, A, B, C, **k)
-
-    def _ready(self, *objs):
-        if self.reducer is None:
-            return
-        if self.folds is not None:
-            self.folds.flush()
-        ps = []
-        for o in objs:
-            ps.extend(o.parameters() if isinstance(o, nn.Module) else [o])
-        self.reducer.section_ready(ps)
 
     # batched per-(image, head) products on the qkv tensor [B, Np, 3, H, hd] and on the score
     # tensors [B, H, Np, NS]
@@ -281,12 +232,8 @@ class CaitEngine:
             ln2, mean2, rstd2 = new(M, D, T), vec(M), vec(M)
             ops.layernorm_fwd(X1, pk.f32(blk.norm2.weight), pk.f32(blk.norm2.bias), ln2, mean2, rstd2,
                               blk.norm2.eps, M=M, D=D)
-            Dh = mlp.fc1.out_features
-            pre, hid = new(M, Dh, T), new(M, Dh, T)
-            self._gemm(ln2, self._w(mlp.fc1.weight), hid, epilogue=EPI_BIAS_GELU, bias=pk.f32(mlp.fc1.bias), C2=pre)
-            X2, f2 = new(M, D, R), new(M, D, T)
-            self._gemm(hid, self._w(mlp.fc2.weight), X2, epilogue=EPI_RESIDUAL, bias=pk.f32(mlp.fc2.bias), R=X1,
-                       gamma=pk.f32(blk.gamma_2), C2=f2)
+            f2 = new(M, D, T)
+            X2, pre, hid = mlp_forward(self, mlp, ln2, X1, save, gamma=pk.f32(blk.gamma_2), C2=f2)
             if save:
                 trunk.append((X, ln1, mean1, rstd1, qkv, S, P, Pm, O, f1, X1, ln2, mean2, rstd2, pre, hid, f2))
             X = X2
@@ -333,66 +280,26 @@ class CaitEngine:
 
         feat, meanf, rstdf = torch.empty((B, D), dtype=f32, device=dev), vec(B), vec(B)
         ops.layernorm_fwd(Cx, pk.f32(m.norm.weight), pk.f32(m.norm.bias), feat, meanf, rstdf, m.norm.eps, M=B, D=D)
-        acts, pres, cur = [feat], [], feat
-        for lin, gelu in self.head:
-            out = torch.empty((B, lin.out_features), dtype=f32, device=dev)
-            bias = pk.f32(lin.bias) if lin.bias is not None else None
-            if gelu:
-                ph = torch.empty_like(out)
-                ops.gemm(cur, pk.f32(lin.weight), out, epilogue=EPI_BIAS_GELU, bias=bias, C2=ph)
-                pres.append(ph)
-            else:
-                ops.gemm(cur, pk.f32(lin.weight), out, bias=bias)
-                pres.append(None)
-            acts.append(out)
-            cur = out
+        out, head_saved = head_forward(pk, self.head, feat)
         if save:
             self.saved = dict(B=B, Np=Np, D=D, H=H, hd=hd, Kp=Kp, NS=NS, patches=patches, trunk=trunk, ca=ca,
-                              Cf=Cx, meanf=meanf, rstdf=rstdf, acts=acts, pres=pres)
-        return cur
+                              Cf=Cx, meanf=meanf, rstdf=rstdf, head=head_saved)
+        return out
 
     # --------------------------------------------------------------- backward ---
-    def backward(self, dout):
-        try:
-            self._backward(dout)
-        except BaseException:
-            if self.folds is not None:
-                self.folds.clear()
-            if self.reducer is not None:
-                self.reducer.abort()
-            raise
-
     def _backward(self, dout):
-        s = self.saved
-        if s is None:
-            raise VitmiError("backward called without a saved forward (or called twice)")
-        self.saved = None
+        s = self._take_saved()
         m, T, R, pk = self.model, self.T, self.R, self.pack
         B, Np, D, H, hd, NS = s["B"], s["Np"], s["D"], s["H"], s["hd"], s["NS"]
         M, N1 = B * Np, Np + 1
         Mu = B * N1
         dev = dout.device
         f32 = torch.float32
-        d = dout.contiguous().float()
 
         def new(r, c, dt):
             return torch.empty((r, c), dtype=dt, device=dev)
 
-        # ---- head
-        acts, pres = s["acts"], s["pres"]
-        if self.head and self.head[-1][1]:
-            raise VitmiError("a head ending in GELU is not supported")
-        for li in range(len(self.head) - 1, -1, -1):
-            lin, _ = self.head[li]
-            ops.gemm(d, acts[li], pk.g(lin.weight), a_kmajor=False, b_kmajor=False)
-            if lin.bias is not None:
-                ops.colsum(d, pk.g(lin.bias))
-            dx = torch.empty((B, lin.in_features), dtype=f32, device=dev)
-            if li > 0 and self.head[li - 1][1]:
-                ops.gemm(d, pk.f32(lin.weight), dx, b_kmajor=False, epilogue=EPI_DGELU, aux=pres[li - 1])
-            else:
-                ops.gemm(d, pk.f32(lin.weight), dx, b_kmajor=False)
-            d = dx
+        d = head_backward(pk, self.head, s["head"], dout.contiguous().float())
 
         # ---- class-attention stage.  Gu [B, Np+1, D]: row 0 = gradient of the CLS stream, rows
         # 1.. = gradient of the trunk output (both CA layers read the same x)
@@ -469,15 +376,8 @@ class CaitEngine:
             blk = tb[bi]
             a, mlp = blk.attn, blk.mlp
             X, ln1, mean1, rstd1, qkv, S, P, Pm, O, f1, X1, ln2, mean2, rstd2, pre, hid, f2 = s["trunk"].pop()
-            Dh = mlp.fc1.out_features
             ops.colsum_mul(G, f2, pk.g(blk.gamma_2), M=M, N=D)
-            dH = new(M, Dh, T)
-            fold = dgelu_gemm_with_bias_grad(self, Gb, self._w(mlp.fc2.weight), dH, pre, pk.g(mlp.fc1.bias))
-            self._gemm(Gb, hid, pk.g(mlp.fc2.weight), a_kmajor=False, b_kmajor=False)
-            dln2 = new(M, D, T)
-            self._gemm(dH, self._w(mlp.fc1.weight), dln2, b_kmajor=False)
-            self._gemm(dH, ln2, pk.g(mlp.fc1.weight), a_kmajor=False, b_kmajor=False)
-            fold()
+            dln2 = mlp_backward(self, mlp, Gb, ln2, pre, hid)
             ops.layernorm_bwd(dln2, X1, mean2, rstd2, pk.f32(blk.norm2.weight), G, G, Gb,
                               pk.g(blk.norm2.weight), pk.g(blk.norm2.bias), gsum=pk.g(a.proj.bias),
                               gb_scale=pk.f32(blk.gamma_1), M=M, D=D, fold=self.folds)
@@ -538,7 +438,3 @@ class CaitEngine:
         if conv.bias is not None:
             ops.colsum(dpos.view(Np, D), pk.g(conv.bias))
         self._ready(m.cls_token, m.pos_embed, m.patch_embed)
-        if self.folds is not None:
-            self.folds.flush()
-        if self.reducer is not None:
-            self.reducer.finish()

@@ -16,7 +16,51 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import EPI_BIAS_GELU, EPI_DGELU, VitmiError
+from .engine import _head_layers, param_grads
 from .packing import ParamPack
+
+
+def head_forward(pack, layers, x):
+    """x [B, in] fp32 through the [(Linear, gelu_after)] layers (engine._head_layers): tiny fp32 GEMMs on the generic MFMA
+    kernel, bias and GELU in the epilogue.  Returns the output and what head_backward needs."""
+    acts, pres, cur = [x], [], x
+    for lin, gelu in layers:
+        out = torch.empty((x.shape[0], lin.out_features), dtype=torch.float32, device=x.device)
+        bias = pack.f32(lin.bias) if lin.bias is not None else None
+        if gelu:
+            pre = torch.empty_like(out)
+            ops.gemm(cur, pack.f32(lin.weight), out, epilogue=EPI_BIAS_GELU, bias=bias, C2=pre)
+        else:
+            pre = None
+            ops.gemm(cur, pack.f32(lin.weight), out, bias=bias)
+        pres.append(pre)
+        acts.append(out)
+        cur = out
+    return cur, (acts, pres)
+
+
+def head_backward(pack, layers, saved, d, need_dx=True):
+    """Backward of head_forward: d = dL/d output (fp32, contiguous).  Writes the layers' gradients into the pack and
+    returns dL/dx (None when not need_dx)."""
+    # z_i = a_i W_i^T + b_i ; a_{i+1} = gelu(z_i) or z_i.  `d` is dL/dz_i on entry;
+    # the inner layer's gelu' is applied by the DGELU epilogue of this layer's dX GEMM.
+    acts, pres = saved
+    if layers and layers[-1][1]:
+        raise VitmiError("a head ending in GELU is not supported")
+    for li in range(len(layers) - 1, -1, -1):
+        lin, _ = layers[li]
+        ops.gemm(d, acts[li], pack.g(lin.weight), a_kmajor=False, b_kmajor=False)
+        if lin.bias is not None:
+            ops.colsum(d, pack.g(lin.bias))
+        if li == 0 and not need_dx:
+            return None
+        dx = torch.empty((d.shape[0], lin.in_features), dtype=torch.float32, device=d.device)
+        if li > 0 and layers[li - 1][1]:
+            ops.gemm(d, pack.f32(lin.weight), dx, b_kmajor=False, epilogue=EPI_DGELU, aux=pres[li - 1])
+        else:
+            ops.gemm(d, pack.f32(lin.weight), dx, b_kmajor=False)
+        d = dx
+    return d
 
 
 class _HeadFn(torch.autograd.Function):
@@ -32,21 +76,13 @@ class _HeadFn(torch.autograd.Function):
         held = head._pack.begin_backward()      # torch's accumulation contract (packing.ParamPack.begin_backward)
         dx = head._backward(dout, ctx.need_dx)
         head._pack.end_backward(held)
-        grads = []
-        for p, gv in zip(head._pack.params, head._pack.fresh_grad_views()):
-            if not p.requires_grad:
-                grads.append(None)
-            elif p.grad is not None and p.grad.data_ptr() == gv.data_ptr():
-                grads.append(None)
-            else:
-                grads.append(gv)
-        return (None, dx, *grads)
+        return (None, dx, *param_grads(head._pack))
 
 
 class ClassifierHead(nn.Sequential):
     def __init__(self, *layers):
         super().__init__(*layers)
-        self._layers = _plan(self)
+        self._layers = _head_layers(self)
         if self._layers is None:
             raise VitmiError("ClassifierHead: layers must be Linear[, GELU], ..., Linear")
         self._pack = None
@@ -80,27 +116,17 @@ class ClassifierHead(nn.Sequential):
 
     # ---- kernels
     def _forward(self, x, save):
-        pk = self._pack
-        acts, pres, cur = [x], [], x
-        for lin, gelu in self._layers:
-            out = torch.empty((x.shape[0], lin.out_features), dtype=torch.float32, device=x.device)
-            bias = pk.f32(lin.bias) if lin.bias is not None else None
-            if gelu:
-                pre = torch.empty_like(out)
-                ops.gemm(cur, pk.f32(lin.weight), out, epilogue=EPI_BIAS_GELU, bias=bias, C2=pre)
-                pres.append(pre)
-            else:
-                ops.gemm(cur, pk.f32(lin.weight), out, bias=bias)
-                pres.append(None)
-            acts.append(out)
-            cur = out
+        out, saved = head_forward(self._pack, self._layers, x)
         if save:
-            self._saved = (acts, pres)
-        return cur
+            self._saved = saved
+        return out
 
     def _backward(self, dout, need_dx):
         try:
-            dx = self._backward_impl(dout, need_dx)
+            if self._saved is None:
+                raise VitmiError("backward called without a saved forward (or called twice)")
+            saved, self._saved = self._saved, None
+            dx = head_backward(self._pack, self._layers, saved, dout.contiguous().float(), need_dx)
         except BaseException:
             if self.reducer is not None:
                 self.reducer.abort()
@@ -109,39 +135,3 @@ class ClassifierHead(nn.Sequential):
             self.reducer.section_ready([p for p in self._pack.params if p.requires_grad])
             self.reducer.finish()
         return dx
-
-    def _backward_impl(self, dout, need_dx):
-        if self._saved is None:
-            raise VitmiError("backward called without a saved forward (or called twice)")
-        acts, pres = self._saved
-        self._saved = None
-        pk = self._pack
-        d = dout.contiguous().float()
-        if self._layers[-1][1]:
-            raise VitmiError("a head ending in GELU is not supported")
-        for li in range(len(self._layers) - 1, -1, -1):
-            lin, _ = self._layers[li]
-            ops.gemm(d, acts[li], pk.g(lin.weight), a_kmajor=False, b_kmajor=False)
-            if lin.bias is not None:
-                ops.colsum(d, pk.g(lin.bias))
-            if li == 0 and not need_dx:
-                return None
-            dx = torch.empty((d.shape[0], lin.in_features), dtype=torch.float32, device=d.device)
-            if li > 0 and self._layers[li - 1][1]:
-                ops.gemm(d, pk.f32(lin.weight), dx, b_kmajor=False, epilogue=EPI_DGELU, aux=pres[li - 1])
-            else:
-                ops.gemm(d, pk.f32(lin.weight), dx, b_kmajor=False)
-            d = dx
-        return d
-
-
-def _plan(seq):
-    """[(Linear, gelu_after)] or None."""
-    out, mods, i = [], list(seq), 0
-    while i < len(mods):
-        if not isinstance(mods[i], nn.Linear):
-            return None
-        gelu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.GELU)
-        out.append((mods[i], gelu))
-        i += 2 if gelu else 1
-    return out

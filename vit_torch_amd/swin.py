@@ -22,15 +22,14 @@ from __future__ import annotations
 
 from typing import Optional
 
-import os
-
 import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import EPI_BIAS_GELU, EPI_DGELU, EPI_RESIDUAL, GEMM_AUTO, VitmiError
-from .packing import ParamPack
-from .vit import Mlp, _DT, _EngineFn, _head_layers, _trunc_normal_, dgelu_gemm_with_bias_grad, engine_gemm
+from ._lib import EPI_RESIDUAL, VitmiError
+from .engine import Engine, EngineModel, mlp_backward, mlp_forward
+from .head import head_backward, head_forward
+from .vit import Mlp, _DT, _trunc_normal_
 
 
 def _relative_position_index(ws):
@@ -121,7 +120,7 @@ class PatchEmbed(nn.Module):
         self.norm = nn.LayerNorm(embed_dim) if patch_norm else None
 
 
-class SwinTransformer(nn.Module):
+class SwinTransformer(EngineModel, nn.Module):
     def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000, embed_dim=96,
                  depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), window_size=7, mlp_ratio=4.0, qkv_bias=True,
                  qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.1, norm_layer=nn.LayerNorm,
@@ -170,19 +169,8 @@ class SwinTransformer(nn.Module):
                 nn.init.zeros_(m.bias)
         self._engine: Optional[SwinEngine] = None
 
-    def engine(self):
-        if self._engine is None or not self._engine.is_current():
-            self._engine = SwinEngine(self)
-        return self._engine
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise VitmiError("vit_torch_amd models run on an MI355X (HIP) device; got a CPU tensor "
-                             "and there is no CPU fallback")
-        eng = self.engine()
-        if torch.is_grad_enabled() and any(p.requires_grad for p in eng.pack.params):
-            return _EngineFn.apply(eng, x, *eng.pack.params)
-        return eng.forward(x, save=False)
+    def _new_engine(self):
+        return SwinEngine(self)
 
 
 configs = {   # models/swin.py:768-820 (the 224 / window-7 classification variants)
@@ -210,32 +198,16 @@ def get_swin_model(arch="swin_tiny_patch4_window7_224", pretrained=False, **kwar
     return SwinTransformer(**cfg)
 
 
-class SwinEngine:
+class SwinEngine(Engine):
     def __init__(self, model: SwinTransformer):
-        self.model = model
+        super().__init__(model)
         dev = model.norm.weight.device
-        if dev.type != "cuda":
-            raise VitmiError("move the model to the GPU before the first forward")
-        self.T, self.R = model.compute_dtype, model.residual_dtype
-        self.split3 = bool(getattr(model, "split3", False))
-        if self.T == torch.float32 and self.R != torch.float32:
-            raise VitmiError("fp32 compute needs an fp32 residual stream")
-        self.head = _head_layers(model.head)
-        if self.head is None:
-            raise VitmiError("head must be Identity, Linear or Sequential(Linear[, GELU], ...)")
-        self.pack = ParamPack(list(model.named_parameters()), dev, shadow=self.T == torch.bfloat16)
-        self.saved = None
-        self.reducer = None
-        # small folds of a backward pass in one launch per flush (ops.FoldQueue; VITMI_DEFER_FOLDS=0: at once)
-        self.folds = ops.FoldQueue() if os.environ.get("VITMI_DEFER_FOLDS", "1") != "0" else None
-        self.profile = None
         # bf16 patch-embed weight at the padded contraction width (see forward); allocated here so
         # that it never lands in a graph's private pool
         Kp = model.patch_embed.proj.weight[0].numel()
         self._pe_kld = max(64, (Kp + 31) // 32 * 32) if self.T == torch.bfloat16 else Kp
         self._pe_wpad = (torch.zeros((model.embed_dim, self._pe_kld), dtype=self.T, device=dev)
                          if self._pe_kld != Kp else None)
-        self.gemm_impl = GEMM_AUTO
         # DropPath keep probabilities of the blocks with a non-zero rate, built ONCE on the device (a torch.tensor(list,
         # device=...) per forward is a pageable-host copy + stream synchronise: not allowed while a HIP graph is capturing
         # — ADVICE r03; the rates are fixed at construction, models/swin.py:531)
@@ -254,26 +226,7 @@ class SwinEngine:
         return keeps == self._dp_rates
 
     def is_current(self):
-        m = self.model
-        return (self.pack.is_current() and m.compute_dtype == self.T and m.residual_dtype == self.R
-                and bool(getattr(m, "split3", False)) == self.split3
-                and len(self.pack.params) == sum(1 for _ in m.parameters()) and self._dp_current())
-
-    def _w(self, p):
-        return self.pack.w(p)
-
-    def _gemm(self, A, B, C, **k):
-        return engine_gemm(self, A, B, C, **k)
-
-    def _ready(self, *objs):
-        if self.reducer is None:
-            return
-        if self.folds is not None:
-            self.folds.flush()
-        ps = []
-        for o in objs:
-            ps.extend(o.parameters() if isinstance(o, nn.Module) else [o])
-        self.reducer.section_ready(ps)
+        return super().is_current() and self._dp_current()
 
     # ---------------------------------------------------------------- forward ---
     def forward(self, x, save: bool):
@@ -364,12 +317,7 @@ class SwinEngine:
                 ln2, mean2, rstd2 = new(M, C, T), vec(M), vec(M)
                 ops.layernorm_fwd(X1, pk.f32(blk.norm2.weight), pk.f32(blk.norm2.bias), ln2, mean2, rstd2,
                                   blk.norm2.eps, M=M, D=C)
-                Dh = mlp.fc1.out_features
-                pre, hid = new(M, Dh, T), new(M, Dh, T)
-                self._gemm(ln2, self._w(mlp.fc1.weight), hid, epilogue=EPI_BIAS_GELU, bias=pk.f32(mlp.fc1.bias), C2=pre)
-                X2 = new(M, C, R)
-                self._gemm(hid, self._w(mlp.fc2.weight), X2, epilogue=EPI_RESIDUAL, bias=pk.f32(mlp.fc2.bias), R=X1,
-                           rowscale=rs2, rows_per_group=L)
+                X2, pre, hid = mlp_forward(self, mlp, ln2, X1, save, rowscale=rs2, rows_per_group=L)
                 if save:
                     blocks.append((X, ln1, mean1, rstd1, qkv, bias, O, lse, X1, ln2, mean2, rstd2, pre, hid, rs1, rs2))
                 X = X2
@@ -396,63 +344,24 @@ class SwinEngine:
         ops.layernorm_fwd(X, pk.f32(m.norm.weight), pk.f32(m.norm.bias), xn, meanf, rstdf, m.norm.eps, M=M, D=C)
         feat = torch.empty((B, C), dtype=f32, device=dev)
         ops.token_mean_fwd(xn, feat, B, L, C)
-        acts, pres, cur = [feat], [], feat
-        for lin, gelu in self.head:
-            out = torch.empty((B, lin.out_features), dtype=f32, device=dev)
-            bias = pk.f32(lin.bias) if lin.bias is not None else None
-            if gelu:
-                ph = torch.empty_like(out)
-                ops.gemm(cur, pk.f32(lin.weight), out, epilogue=EPI_BIAS_GELU, bias=bias, C2=ph)
-                pres.append(ph)
-            else:
-                ops.gemm(cur, pk.f32(lin.weight), out, bias=bias)
-                pres.append(None)
-            acts.append(out)
-            cur = out
+        out, head_saved = head_forward(pk, self.head, feat)
         if save:
             self.saved = dict(B=B, patches=patches, pe=pe_saved, stages=stages, Xf=X, meanf=meanf, rstdf=rstdf,
-                              acts=acts, pres=pres, L=L)
-        return cur
+                              head=head_saved, L=L)
+        return out
 
     # --------------------------------------------------------------- backward ---
-    def backward(self, dout):
-        try:
-            self._backward(dout)
-        except BaseException:
-            if self.folds is not None:
-                self.folds.clear()
-            if self.reducer is not None:
-                self.reducer.abort()
-            raise
-
     def _backward(self, dout):
-        s = self.saved
-        if s is None:
-            raise VitmiError("backward called without a saved forward (or called twice)")
-        self.saved = None
+        s = self._take_saved()
         m, T, R, pk = self.model, self.T, self.R, self.pack
         B = s["B"]
         dev = dout.device
         f32 = torch.float32
-        d = dout.contiguous().float()
 
         def new(r, c, dt):
             return torch.empty((r, c), dtype=dt, device=dev)
 
-        acts, pres = s["acts"], s["pres"]
-        if self.head and self.head[-1][1]:
-            raise VitmiError("a head ending in GELU is not supported")
-        for li in range(len(self.head) - 1, -1, -1):
-            lin, _ = self.head[li]
-            ops.gemm(d, acts[li], pk.g(lin.weight), a_kmajor=False, b_kmajor=False)
-            if lin.bias is not None:
-                ops.colsum(d, pk.g(lin.bias))
-            dx = torch.empty((B, lin.in_features), dtype=f32, device=dev)
-            if li > 0 and self.head[li - 1][1]:
-                ops.gemm(d, pk.f32(lin.weight), dx, b_kmajor=False, epilogue=EPI_DGELU, aux=pres[li - 1])
-            else:
-                ops.gemm(d, pk.f32(lin.weight), dx, b_kmajor=False)
-            d = dx
+        d = head_backward(pk, self.head, s["head"], dout.contiguous().float())
 
         # token mean + final norm
         L, C = s["L"], m.num_features
@@ -500,14 +409,7 @@ class SwinEngine:
                 ws, sh, H = blk.window_size, blk.shift_size, a.num_heads
                 hd, N = C // H, ws * ws
                 Bw = B * (Hh // ws) * (Ww // ws)
-                Dh = mlp.fc1.out_features
-                dH = new(M, Dh, T)
-                fold = dgelu_gemm_with_bias_grad(self, Gb, self._w(mlp.fc2.weight), dH, pre, pk.g(mlp.fc1.bias))
-                self._gemm(Gb, hid, pk.g(mlp.fc2.weight), a_kmajor=False, b_kmajor=False)
-                dln2 = new(M, C, T)
-                self._gemm(dH, self._w(mlp.fc1.weight), dln2, b_kmajor=False)
-                self._gemm(dH, ln2, pk.g(mlp.fc1.weight), a_kmajor=False, b_kmajor=False)
-                fold()
+                dln2 = mlp_backward(self, mlp, Gb, ln2, pre, hid)
                 ops.layernorm_bwd(dln2, X1, mean2, rstd2, pk.f32(blk.norm2.weight), G, G, Gb,
                                   pk.g(blk.norm2.weight), pk.g(blk.norm2.bias), gsum=pk.g(a.proj.bias),
                                   gb_rowscale=rs1, rows_per_group=L, M=M, D=C, fold=self.folds)
@@ -555,7 +457,3 @@ class SwinEngine:
         else:
             self._gemm(Gb, s["patches"], pk.g(pe.proj.weight).view(C, Kp), a_kmajor=False, b_kmajor=False)
         self._ready(m.patch_embed)
-        if self.folds is not None:
-            self.folds.flush()
-        if self.reducer is not None:
-            self.reducer.finish()

@@ -15,17 +15,15 @@ autograd, utils_network.py:441).  There is no PyTorch fallback.
 """
 from __future__ import annotations
 
-import math
-import os
-from typing import List, Optional
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import (EPI_BIAS_GELU, EPI_DGELU, EPI_PATCH_POS, EPI_RESIDUAL, EPI_STORE, GEMM_AUTO,
-                   LAUNCH_ROWS_PADDED, VitmiError)
-from .packing import ParamPack
+from ._lib import EPI_BIAS_GELU, EPI_DGELU, EPI_PATCH_POS, EPI_RESIDUAL, VitmiError
+from .engine import Engine, EngineModel, engine_wgrad_pair, mlp_backward, mlp_forward
+from .head import head_backward, head_forward
 from .posembed import tables_for
 from .data import PatchRows
 
@@ -76,7 +74,7 @@ def _trunc_normal_(t, std=0.02):
     return nn.init.trunc_normal_(t, std=std)
 
 
-class VisionTransformer(nn.Module):
+class VisionTransformer(EngineModel, nn.Module):
     """`apply_head=False` reproduces upstream DINO, whose forward returns
     norm(x)[:, 0] and never calls `.head` ([recall]); the factory
     passes `apply_head=True` when it installs a classifier."""
@@ -118,188 +116,12 @@ class VisionTransformer(nn.Module):
                 nn.init.zeros_(m.bias)
         self._engine: Optional[VitEngine] = None
 
-    def engine(self) -> "VitEngine":
-        if self._engine is None or not self._engine.is_current():
-            self._engine = VitEngine(self)
-        return self._engine
-
-    def forward(self, x):
-        if not x.is_cuda:
-            raise VitmiError("vit_torch_amd models run on an MI355X (HIP) device; got a CPU tensor "
-                             "and there is no CPU fallback")
-        eng = self.engine()
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in eng.pack.params)
-        if need_grad:
-            return _EngineFn.apply(eng, x, *eng.pack.params)
-        return eng.forward(x, save=False)
-
-
-class _EngineFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, eng, x, *params):
-        ctx.eng = eng
-        return eng.forward(x, save=True)
-
-    @staticmethod
-    def backward(ctx, dout):
-        eng = ctx.eng
-        held = eng.pack.begin_backward()        # .grad tensors that alias the flat buffer: accumulate, do not overwrite
-        eng.backward(dout)
-        eng.pack.end_backward(held)
-        grads = []
-        for p, gv in zip(eng.pack.params, eng.pack.fresh_grad_views()):
-            if not p.requires_grad:
-                grads.append(None)
-            elif p.grad is not None and p.grad.data_ptr() == gv.data_ptr():
-                grads.append(None)      # .grad already IS this buffer (zero_grad(set_to_none=False))
-            else:
-                grads.append(gv)
-        return (None, None, *grads)
+    def _new_engine(self) -> "VitEngine":
+        return VitEngine(self)
 
 
 # ------------------------------------------------------------------ engine --
-def _head_layers(head) -> Optional[List[tuple]]:
-    """[(Linear, gelu_after)] for Identity / Linear / Sequential(Linear[,GELU]...) heads
-    (/root/reference/models/vision_all.py:299-320); None if the head is something else."""
-    if isinstance(head, nn.Identity):
-        return []
-    if isinstance(head, nn.Linear):
-        return [(head, False)]
-    if isinstance(head, nn.Sequential):
-        out = []
-        mods = list(head)
-        i = 0
-        while i < len(mods):
-            if not isinstance(mods[i], nn.Linear):
-                return None
-            gelu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.GELU)
-            out.append((mods[i], gelu))
-            i += 2 if gelu else 1
-        return out
-    return None
-
-
-def _timing_events(eng):
-    """Two timing events for one launch of the instrumented step.  `eng.profile_external`: the step is being CAPTURED into a
-    HIP graph — `external` events become event-record nodes of the graph, so the per-launch durations are those of the
-    replayed graph (the launch form bench.py times), not of an eager step."""
-    ext = bool(getattr(eng, "profile_external", False))
-    return (torch.cuda.Event(enable_timing=True, external=ext), torch.cuda.Event(enable_timing=True, external=ext))
-
-
-def _rows_padded(*tensors) -> bool:
-    """True when every given [M, .] tensor's storage reaches ceil256(M) rows at its row stride."""
-    for t in tensors:
-        if t is None or t.dim() != 2:
-            continue
-        rows = (t.shape[0] + 255) // 256 * 256
-        need = (t.storage_offset() + (rows - 1) * t.stride(0) + t.shape[1]) * t.element_size()
-        if t.untyped_storage().nbytes() < need:
-            return False
-    return True
-
-
-def _engine_gemm_split3(eng, A, B, C, **k):
-    """engine_gemm in the "bf16x3" mode: fp32 operands -> three-part bf16 images -> ONE bf16 product over 3K on the tile
-    kernels, fp32 epilogue (ops.gemm_split3).  Profiled launches count the algorithmic 2 M N K FLOPs (the mode's own
-    roofline is a third of the bf16 peak)."""
-    if eng.reducer is not None:
-        k.setdefault("launch_flags", eng.reducer.launch_flags())
-    if k.get("C2") is not None and k.get("epilogue") == EPI_RESIDUAL:
-        # CaiT's LayerScale residual x + gamma * f(x) with the branch output f kept for d gamma (models/cait.py:143-150): the
-        # tile kernel writes that second output in the OPERAND dtype (bf16 here), so the mode takes three steps, each the
-        # reference's own rounding: f = A W^T + b (three-product GEMM, fp32), out = gamma * f, out += x
-        if k.get("rowscale") is not None or not (C.is_contiguous() and k["R"].is_contiguous()):
-            raise VitmiError("compute_dtype='bf16x3': LayerScale residual with a DropPath row scale / strided rows is not built")
-        f, R_, gamma = k.pop("C2"), k.pop("R"), k.pop("gamma", None)
-        k.pop("epilogue")
-        _engine_gemm_split3(eng, A, B, f, **k)
-        ops.scale_cast(f, C, gamma, M=C.shape[0], N=C.shape[1])
-        ops.axpy(R_.reshape(-1), C.reshape(-1), 1.0)
-        return C
-    if eng.profile is None:
-        return ops.gemm_split3(A, B, C, **k)
-    akm, bkm = k.get("a_kmajor", True), k.get("b_kmajor", True)
-    Kdim = A.shape[1] if akm else A.shape[0]
-    e0, e1 = _timing_events(eng)
-    e0.record()
-    ops.gemm_split3(A, B, C, **k)
-    e1.record()
-    name = "gemm3_" + ("n" if akm else "t") + ("t" if bkm else "n")
-    eng.profile.append((name, (C.shape[0], C.shape[1], Kdim), 2.0 * C.shape[0] * C.shape[1] * Kdim, e0, e1))
-    return C
-
-
-def engine_gemm(eng, A, B, C, **k):
-    """ops.gemm with the engine's implementation switch; when eng.profile is a list, each
-    launch is bracketed by HIP events on the launch stream (bench.py's roofline leg)."""
-    # the block MLPs keep gelu'(pre) instead of pre in bf16 mode: the GELU epilogue has the exp
-    # at hand, and the backward epilogue becomes a multiply (vitmi_gemm_desc.aux_is_derivative).
-    # fp32 (parity) mode keeps the pre-activation, as the reference's autograd does.
-    if getattr(eng, "split3", False) and A.dtype == torch.float32:
-        return _engine_gemm_split3(eng, A, B, C, **k)
-    if k.get("epilogue") in (EPI_BIAS_GELU, EPI_DGELU):
-        k.setdefault("aux_deriv", eng.T == torch.bfloat16)
-    if eng.reducer is not None:             # gradient buckets in flight: share the device with RCCL's kernels
-        k.setdefault("launch_flags", eng.reducer.launch_flags())
-    if getattr(eng, "pad_rows", False) and _rows_padded(C, k.get("C2"), k.get("R"), k.get("aux")):
-        # every [M, .] activation of this engine comes from _alloc (rows rounded up to 256); the flag is only passed when the
-        # storage behind each row-indexed output / side input really covers the padding (ADVICE r04: a future torch.empty
-        # output would otherwise be a silent out-of-bounds write of up to 255 rows)
-        k["launch_flags"] = k.get("launch_flags", 0) | LAUNCH_ROWS_PADDED
-    if eng.profile is None:
-        return ops.gemm(A, B, C, impl=eng.gemm_impl, **k)
-    akm, bkm = k.get("a_kmajor", True), k.get("b_kmajor", True)
-    Kdim = A.shape[1] if akm else A.shape[0]
-    e0, e1 = _timing_events(eng)
-    e0.record()
-    ops.gemm(A, B, C, impl=eng.gemm_impl, **k)
-    e1.record()
-    name = "gemm_" + ("n" if akm else "t") + ("t" if bkm else "n")
-    eng.profile.append((name, (C.shape[0], C.shape[1], Kdim), 2.0 * C.shape[0] * C.shape[1] * Kdim, e0, e1))
-    return C
-
-
-def engine_wgrad_pair(eng, dY0, X0, dW0, dY1, X1, dW1):
-    """dW0 = dY0^T X0 and dW1 = dY1^T X1 (the proj and qkv weight gradients of an attention block) in one launch where
-    the library pairs them (ops.gemm_pair / vitmi_gemm_pair), else as two GEMMs."""
-    paired = (eng.gemm_impl == GEMM_AUTO and dY0.dtype == torch.bfloat16 and dW0.dtype == torch.float32
-              and ops.gemm_pair_shares_a_launch(dW0.shape[0], dW0.shape[1], dW1.shape[0], dW1.shape[1], dY0.shape[0]))
-    if not paired:
-        eng._gemm(dY0, X0, dW0, a_kmajor=False, b_kmajor=False)
-        eng._gemm(dY1, X1, dW1, a_kmajor=False, b_kmajor=False)
-        return
-    flags = eng.reducer.launch_flags() if eng.reducer is not None else 0
-    if eng.profile is None:
-        ops.gemm_pair(dY0, X0, dW0, dY1, X1, dW1, launch_flags=flags)
-        return
-    e0, e1 = _timing_events(eng)
-    e0.record()
-    ops.gemm_pair(dY0, X0, dW0, dY1, X1, dW1, launch_flags=flags)
-    e1.record()
-    K = dY0.shape[0]
-    flops = 2.0 * K * (dW0.shape[0] * dW0.shape[1] + dW1.shape[0] * dW1.shape[1])
-    eng.profile.append(("gemm_tn_pair", (dW0.shape[0] + dW1.shape[0], dW0.shape[1], K), flops, e0, e1))
-
-
-def dgelu_gemm_with_bias_grad(eng, Gb, W2, dH, pre, bias_grad):
-    """dH = (Gb @ W2) * gelu'(pre) and bias_grad = column sums of dH.  On the bf16 tile paths
-    the sums ride on the GEMM epilogue as per-128-row partials (a few MB, folded by colsum);
-    otherwise dH is summed by a separate pass.  Returns a thunk that performs the fold /
-    pass (callers may run it on a side stream)."""
-    M, Dh = dH.shape
-    K = Gb.shape[1]
-    fused = (dH.dtype == torch.bfloat16 and eng.gemm_impl == GEMM_AUTO
-             and ops.gemm_uses_fast(M, Dh, K, b_kmajor=False, epilogue=EPI_DGELU, colsum_part=True))
-    if fused:
-        part = torch.empty(((M + 127) // 128, Dh), dtype=torch.float32, device=dH.device)
-        eng._gemm(Gb, W2, dH, b_kmajor=False, epilogue=EPI_DGELU, aux=pre, colsum_part=part)
-        return lambda: ops.colsum(part, bias_grad, fold=getattr(eng, "folds", None))
-    eng._gemm(Gb, W2, dH, b_kmajor=False, epilogue=EPI_DGELU, aux=pre)
-    return lambda: ops.colsum(dH, bias_grad)
-
-
-class VitEngine:
+class VitEngine(Engine):
     """Executes VisionTransformer forward / backward as a fixed kernel sequence.
 
     Activations of type T (compute dtype: bf16, or fp32 in parity mode), residual
@@ -308,71 +130,20 @@ class VitEngine:
     """
 
     def __init__(self, model: VisionTransformer):
-        self.model = model
-        dev = model.pos_embed.device
-        if dev.type != "cuda":
-            raise VitmiError("move the model to the GPU before the first forward")
-        self.T = model.compute_dtype
-        self.R = model.residual_dtype
-        self.split3 = bool(getattr(model, "split3", False))
-        if self.T == torch.float32 and self.R != torch.float32:
-            raise VitmiError("fp32 compute needs an fp32 residual stream")
-        self.head = _head_layers(model.head) if model.apply_head else []
-        if self.head is None:
-            raise VitmiError("head must be Identity, Linear or Sequential(Linear[, GELU], ...)")
-        named = [(n, p) for n, p in model.named_parameters()]
-        self.pack = ParamPack(named, dev, shadow=self.T == torch.bfloat16)
-        self.saved = None
-        self.gemm_impl = GEMM_AUTO
-        self.reducer = None          # ddp.GradReducer: told when a section's grads are final
-        self.profile = None          # list of (name, flops, start_event, end_event) when profiling
-        # (round 1 ran the weight-gradient GEMMs on a second HIP stream; A/B on one box,
-        # profiles/r02_ab_overlap*: 38.47-38.67 ms/step without it, 38.55-39.26 with it — a
-        # 256x256-tile GEMM workgroup owns its CU's whole register file and 128 KiB of LDS, so
-        # two GEMM kernels only take CUs from each other.  Removed.)
-        self.fused_bias_grads = os.environ.get("VITMI_FUSED_BIAS_GRADS", "1") != "0"
-        # the ~50 small folds of a backward pass (LayerNorm dgamma | dbeta | bias sums, fc1 / qkv bias partials) run as
-        # ONE launch per flush instead of one each (ops.FoldQueue; VITMI_DEFER_FOLDS=0: fold at once, for A/B)
-        self.folds = ops.FoldQueue() if os.environ.get("VITMI_DEFER_FOLDS", "1") != "0" else None
+        super().__init__(model)
         # Row padding (round 4): M = B * N is a multiple of the 256-row GEMM tile only for special batch sizes (197 B: B % 256
         # == 0).  Every [M, .] activation is allocated to the next multiple of 256 rows and used through its [:M] view; the
         # GEMM calls carry VITMI_LAUNCH_ROWS_PADDED, so a ragged M runs on the 256x256 tile kernel (last row tile: A's last row
-        # repeated, surplus output rows into the padding) instead of the slower 256x128 ragged form.  VITMI_PAD_ROWS=0: off.
-        self.pad_rows = self.T == torch.bfloat16 and os.environ.get("VITMI_PAD_ROWS", "1") != "0"
-        self.cls_last = bool(getattr(model, "cls_only_last_block", False))
+        # repeated, surplus output rows into the padding) instead of the slower 256x128 ragged form.
+        self.pad_rows = self.T == torch.bfloat16
+        self.cls_last = bool(model.cls_only_last_block)
         if self.cls_last and model.embed_dim // model.blocks[0].attn.num_heads > 64:
             # the one-query form runs on the class-attention kernels (cait_ops.hip): hd <= 64 (and N <= 256, checked per input)
             raise VitmiError("cls_only_last_block needs head_dim <= 64 (the class-attention kernels' limit); got "
                              f"{model.embed_dim // model.blocks[0].attn.num_heads}: build the model without the option")
 
-    def _alloc(self, rows, cols, dt, dev, zero=False):
-        r = (rows + 255) // 256 * 256 if self.pad_rows else rows
-        t = (torch.zeros if zero else torch.empty)((r, cols), dtype=dt, device=dev)
-        return t[:rows]
-
     def is_current(self) -> bool:
-        m = self.model
-        return (self.pack.is_current() and m.compute_dtype == self.T and m.residual_dtype == self.R
-                and bool(getattr(m, "split3", False)) == self.split3
-                and len(self.pack.params) == sum(1 for _ in m.parameters())
-                and bool(getattr(m, "cls_only_last_block", False)) == self.cls_last)
-
-    # -- helpers -------------------------------------------------------------
-    def _w(self, p):
-        return self.pack.w(p)
-
-    def _gemm(self, A, B, C, **k):
-        return engine_gemm(self, A, B, C, **k)
-
-    def _ready(self, *mods_or_params):
-        if self.reducer is None:
-            return
-        if self.folds is not None:
-            self.folds.flush()              # the section's bias / LayerNorm gradients must be final before its bucket leaves
-        ps = []
-        for o in mods_or_params:
-            ps.extend(o.parameters() if isinstance(o, nn.Module) else [o])
-        self.reducer.section_ready(ps)
+        return super().is_current() and bool(self.model.cls_only_last_block) == self.cls_last
 
     def _pos_for(self, gh, gw):
         """pos_embed at the input's patch grid: as stored, or the bicubic resize upstream DINO
@@ -454,14 +225,7 @@ class VitEngine:
             rstd2 = torch.empty(M, dtype=torch.float32, device=dev)
             ops.layernorm_fwd(X1, self.pack.f32(blk.norm2.weight), self.pack.f32(blk.norm2.bias), ln2,
                               mean2, rstd2, blk.norm2.eps, M=M, D=D)
-            Dh = mlp.fc1.out_features
-            pre = new(M, Dh, T) if save else None       # what the backward needs of fc1's output (engine_gemm)
-            hid = new(M, Dh, T)
-            self._gemm(ln2, self._w(mlp.fc1.weight), hid, epilogue=EPI_BIAS_GELU,
-                       bias=self.pack.f32(mlp.fc1.bias), C2=pre)
-            X2 = new(M, D, R)
-            self._gemm(hid, self._w(mlp.fc2.weight), X2, epilogue=EPI_RESIDUAL,
-                       bias=self.pack.f32(mlp.fc2.bias), R=X1)
+            X2, pre, hid = mlp_forward(self, mlp, ln2, X1, save)
             if save:
                 blocks.append((X, ln1, mean1, rstd1, qkv, O, lse, X1, ln2, mean2, rstd2, pre, hid))
             X = X2
@@ -471,27 +235,12 @@ class VitEngine:
         xf_stride = D if last_cls is not None else N * D       # the CLS-only last block leaves a [B, D] stream
         ops.layernorm_fwd(X, self.pack.f32(m.norm.weight), self.pack.f32(m.norm.bias), feat, meanf,
                           rstdf, m.norm.eps, M=B, D=D, x_stride=xf_stride, y_stride=D)
-        # classifier head: tiny fp32 GEMMs on the generic MFMA kernel
-        acts = [feat]
-        pres = []
-        cur = feat
-        for lin, gelu in self.head:
-            out = torch.empty((B, lin.out_features), dtype=torch.float32, device=dev)
-            bias = self.pack.f32(lin.bias) if lin.bias is not None else None
-            if gelu:
-                pre_h = torch.empty_like(out)
-                ops.gemm(cur, self.pack.f32(lin.weight), out, epilogue=EPI_BIAS_GELU, bias=bias, C2=pre_h)
-                pres.append(pre_h)
-            else:
-                ops.gemm(cur, self.pack.f32(lin.weight), out, bias=bias)
-                pres.append(None)
-            acts.append(out)
-            cur = out
+        out, head_saved = head_forward(self.pack, self.head, feat)
         if save:
             self.saved = dict(B=B, N=N, M=M, D=D, H=H, hd=hd, Kp=Kp, patches=patches, blocks=blocks,
-                              Xf=X, meanf=meanf, rstdf=rstdf, acts=acts, pres=pres,
+                              Xf=X, meanf=meanf, rstdf=rstdf, head=head_saved,
                               pos_tabs=pos_tabs, last_cls=last_cls)
-        return cur
+        return out
 
     # -- the last block on the CLS row only (cls_only_last_block) ------------------
     def _last_block_cls_fwd(self, blk, X, B, N, M, D, H, hd, save, new, dev):
@@ -590,47 +339,16 @@ class VitEngine:
         return G, (G if Gb is None else Gb)
 
     # -- backward ------------------------------------------------------------
-    def backward(self, dout):
-        try:
-            self._backward(dout)
-        except BaseException:
-            if self.folds is not None:
-                self.folds.clear()
-            if self.reducer is not None:
-                self.reducer.abort()
-            raise
-
     def _backward(self, dout):
-        s = self.saved
-        if s is None:
-            raise VitmiError("backward called without a saved forward (or called twice)")
-        self.saved = None
+        s = self._take_saved()
         m, T, R, pk = self.model, self.T, self.R, self.pack
         B, N, M, D, H, hd = s["B"], s["N"], s["M"], s["D"], s["H"], s["hd"]
         dev = dout.device
-        d = dout.contiguous().float()
 
         def new(rows, cols, dt):
             return self._alloc(rows, cols, dt, dev)
 
-        # ---- classifier head (fp32, generic MFMA kernel) ----
-        # z_i = a_i W_i^T + b_i ; a_{i+1} = gelu(z_i) or z_i.  `d` is dL/dz_i on entry;
-        # the inner layer's gelu' is applied by the DGELU epilogue of this layer's dX GEMM.
-        acts, pres = s["acts"], s["pres"]
-        if self.head and self.head[-1][1]:
-            raise VitmiError("a head ending in GELU is not supported")
-        for li in range(len(self.head) - 1, -1, -1):
-            lin, _ = self.head[li]
-            ops.gemm(d, acts[li], pk.g(lin.weight), a_kmajor=False, b_kmajor=False)
-            if lin.bias is not None:
-                ops.colsum(d, pk.g(lin.bias))
-            dx = torch.empty((B, lin.in_features), dtype=torch.float32, device=dev)
-            if li > 0 and self.head[li - 1][1]:
-                ops.gemm(d, pk.f32(lin.weight), dx, b_kmajor=False, epilogue=EPI_DGELU, aux=pres[li - 1])
-            else:
-                ops.gemm(d, pk.f32(lin.weight), dx, b_kmajor=False)
-            d = dx
-        dfeat = d
+        dfeat = head_backward(pk, self.head, s["head"], dout.contiguous().float())
 
         # ---- final LayerNorm on the CLS rows -> residual-stream gradient G ----
         blocks_list = list(m.blocks)
@@ -662,8 +380,6 @@ class VitEngine:
                 ops.cast(G, Gb)
         gb_out = None if T == R else Gb
 
-        fused_bias = self.fused_bias_grads and T == torch.bfloat16 and self.gemm_impl == GEMM_AUTO
-
         saved_blocks = s["blocks"]
         for bi in range(len(blocks_list) - 1, -1, -1):
             blk = blocks_list[bi]
@@ -671,21 +387,8 @@ class VitEngine:
             X, ln1, mean1, rstd1, qkv, O, lse, X1, ln2, mean2, rstd2, pre, hid = sv
             del sv
             a, mlp = blk.attn, blk.mlp
-            Dh = mlp.fc1.out_features
             # MLP branch
-            dH = new(M, Dh, T)
-            # bias gradients ride on the kernels that produce dH / dqkv (per-row-block column
-            # sums, folded by a tiny colsum) whenever those kernels are the bf16 fast ones
-            dH_part = None
-            if fused_bias and ops.gemm_uses_fast(M, Dh, D, b_kmajor=False, epilogue=EPI_DGELU, colsum_part=True):
-                dH_part = torch.empty(((M + 127) // 128, Dh), dtype=torch.float32, device=dev)
-            self._gemm(Gb, self._w(mlp.fc2.weight), dH, b_kmajor=False, epilogue=EPI_DGELU, aux=pre,
-                       **({"colsum_part": dH_part} if dH_part is not None else {}))
-            self._gemm(Gb, hid, pk.g(mlp.fc2.weight), a_kmajor=False, b_kmajor=False)
-            self._gemm(dH, ln2, pk.g(mlp.fc1.weight), a_kmajor=False, b_kmajor=False)
-            ops.colsum(dH_part if dH_part is not None else dH, pk.g(mlp.fc1.bias), fold=self.folds)
-            dln2 = new(M, D, T)
-            self._gemm(dH, self._w(mlp.fc1.weight), dln2, b_kmajor=False)
+            dln2 = mlp_backward(self, mlp, Gb, ln2, pre, hid)
             ops.layernorm_bwd(dln2, X1, mean2, rstd2, pk.f32(blk.norm2.weight), G, G, gb_out,
                               pk.g(blk.norm2.weight), pk.g(blk.norm2.bias), gsum=pk.g(a.proj.bias),
                               M=M, D=D, fold=self.folds)
@@ -693,8 +396,9 @@ class VitEngine:
             dO = new(M, D, T)
             self._gemm(Gb, self._w(a.proj.weight), dO, b_kmajor=False)
             dqkv = new(M, 3 * D, T)
+            # the qkv bias gradient rides on the attention backward (per-row-block column sums, folded by a tiny colsum)
             dqkv_part = None
-            if fused_bias and a.qkv.bias is not None:
+            if T == torch.bfloat16 and a.qkv.bias is not None:
                 dqkv_part = torch.empty((ops.attn_bwd_dbias_rows(B, N), 3 * D), dtype=torch.float32, device=dev)
             ops.attn_bwd(qkv, O, dO, lse, dqkv, B, N, H, hd, a.scale, dbias_part=dqkv_part,
                          launch_flags=self.reducer.launch_flags() if self.reducer is not None else 0)
@@ -727,7 +431,3 @@ class VitEngine:
         if conv.bias is not None:
             ops.colsum(dpos[D:].view(N - 1, D), pk.g(conv.bias))  # CLS rows carry no conv bias
         self._ready(m.cls_token, m.pos_embed, m.patch_embed)
-        if self.folds is not None:
-            self.folds.flush()
-        if self.reducer is not None:
-            self.reducer.finish()
