@@ -288,7 +288,7 @@ int vitmi_colsum_mul(const void* x, int x_dtype, int64_t ldx, const void* y, int
  * (Shifted-)window attention, models/swin.py:113-144 inside SwinTransformerBlock.forward
  * :241-261.  qkv [B*L, 3*H*hd] and out/dout [B*L, H*hd] stay in TOKEN order: the cyclic
  * shift, window_partition and window_reverse are folded into the kernels' row addressing.
- * Bw = B * (Himg/ws) * (Wimg/ws) windows of N = ws*ws <= 64 tokens; bias [H,N,N] fp32 (the
+ * Bw = B * (Himg/ws) * (Wimg/ws) windows of N = ws*ws <= 144 tokens (window 12); bias [H,N,N] fp32 (the
  * gathered relative position bias), mask [nW,N,N] fp32 or NULL (shift mask, -100/0);
  * lse [Bw,H,N]. */
 int vitmi_win_attn_fwd(const void* qkv, void* out, float* lse, const float* bias, const float* mask,

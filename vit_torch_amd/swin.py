@@ -173,11 +173,14 @@ class SwinTransformer(EngineModel, nn.Module):
         return SwinEngine(self)
 
 
-configs = {   # models/swin.py:768-820 (the 224 / window-7 classification variants)
+configs = {   # models/swin.py:768-820 (the 'crop' key of the 384 variants is dropped, as the model never reads it)
     "swin_tiny_patch4_window7_224": dict(drop_path_rate=0.2, embed_dim=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24], window_size=7),
     "swin_small_patch4_window7_224": dict(drop_path_rate=0.3, embed_dim=96, depths=[2, 2, 18, 2], num_heads=[3, 6, 12, 24], window_size=7),
     "swin_base_patch4_window7_224": dict(drop_path_rate=0.5, embed_dim=128, depths=[2, 2, 18, 2], num_heads=[4, 8, 16, 32], window_size=7),
     "swin_large_patch4_window7_224": dict(embed_dim=192, depths=[2, 2, 18, 2], num_heads=[6, 12, 24, 48], window_size=7),
+    "swin_base_patch4_window12_384": dict(img_size=384, embed_dim=128, depths=[2, 2, 18, 2], num_heads=[4, 8, 16, 32], window_size=12),
+    "swin_large_patch4_window12_384": dict(img_size=384, embed_dim=192, depths=[2, 2, 18, 2], num_heads=[6, 12, 24, 48], window_size=12),
+    "swin_tiny_c24_patch4_window8_256": dict(img_size=256, drop_path_rate=0.2, embed_dim=96, depths=[2, 2, 6, 2], num_heads=[4, 8, 16, 32], window_size=8),
 }
 
 

@@ -25,9 +25,13 @@ class VisionModelZoo:
         # models/vision_all.py:44-49 / models/cait.py:13-18
         "cait": ["cait_M48", "cait_M36", "cait_S36", "cait_S24", "cait_S24_224", "cait_XS24", "cait_XXS24",
                  "cait_XXS24_224", "cait_XXS36", "cait_XXS36_224"],
-        # models/vision_all.py:50-69 (the 224 / window-7 classification variants)
+        # models/vision_all.py:50-69, plus swin_large_patch4_window7_224; the _22k / _22kto1k names resolve by prefix
         "swin": ["swin_tiny_patch4_window7_224", "swin_small_patch4_window7_224", "swin_base_patch4_window7_224",
-                 "swin_large_patch4_window7_224"],
+                 "swin_large_patch4_window7_224", "swin_base_patch4_window12_384",
+                 "swin_base_patch4_window7_224_22k", "swin_base_patch4_window7_224_22kto1k",
+                 "swin_base_patch4_window12_384_22k", "swin_base_patch4_window12_384_22kto1k",
+                 "swin_large_patch4_window7_224_22k", "swin_large_patch4_window7_224_22kto1k",
+                 "swin_large_patch4_window12_384_22k", "swin_large_patch4_window12_384_22kto1k"],
     }
     # name: (patch, embed_dim, depth, heads) — DINO vit_small / vit_base
     dino_cfg = {
