@@ -5,6 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from swin_util import torch_window_attention
 from util import assert_close, bf16_round
 
 pytestmark = pytest.mark.gpu
@@ -18,33 +19,6 @@ def gen(shape, seed, scale=1.0):
 def ops(lib):
     from vit_torch_amd import ops as _o
     return _o
-
-
-def torch_window_attention(qkv, do, bias, B, Hh, Ww, ws, shift, H, hd):
-    """roll -> window_partition -> attention(+bias,+mask) -> window_reverse -> roll back (models/swin.py:241-261);
-    returns (out, mask, dqkv, dbias)."""
-    from oracle.swin_ref import shift_attn_mask, window_partition, window_reverse
-    C, N, L = H * hd, ws * ws, Hh * Ww
-    scale = hd ** -0.5
-    mask = shift_attn_mask(Hh, Ww, ws, shift) if shift > 0 else None
-    qr = qkv.clone().requires_grad_(True)
-    br = bias.clone().requires_grad_(True)
-    x = qr.view(B, Hh, Ww, 3 * C)
-    if shift:
-        x = torch.roll(x, shifts=(-shift, -shift), dims=(1, 2))
-    xw = window_partition(x, ws).view(-1, N, 3, H, hd).permute(2, 0, 3, 1, 4)
-    q, k, v = xw[0] * scale, xw[1], xw[2]
-    attn = q @ k.transpose(-2, -1) + br.unsqueeze(0)
-    if mask is not None:
-        nW = mask.shape[0]
-        attn = (attn.view(B, nW, H, N, N) + mask.unsqueeze(1).unsqueeze(0)).view(-1, H, N, N)
-    o = (attn.softmax(-1) @ v).transpose(1, 2).reshape(-1, ws, ws, C)
-    o = window_reverse(o, ws, Hh, Ww)
-    if shift:
-        o = torch.roll(o, shifts=(shift, shift), dims=(1, 2))
-    o = o.reshape(B, L, C)
-    o.backward(do)
-    return o.detach(), mask, qr.grad, br.grad
 
 
 CASES = [(2, 24, 24, 12, 0, 2, 32), (1, 24, 24, 12, 6, 3, 32), (2, 12, 12, 12, 0, 4, 32), (1, 24, 24, 12, 6, 2, 16),
@@ -64,7 +38,7 @@ def test_window12_attention_in_token_order(ops, lib, mfma, dt, B, Hh, Ww, ws, sh
     qkv = rd(gen((B, L, 3 * C), 1))
     do = rd(gen((B, L, C), 2))
     bias = gen((H, N, N), 3, 0.5)
-    o, mask, dq_ref, db_ref = torch_window_attention(qkv, do, bias, B, Hh, Ww, ws, shift, H, hd)
+    o, mask, dq_ref, db_ref = torch_window_attention(qkv, do, bias, B, Hh, Ww, ws, shift, H, hd)[:4]
     Bw = B * (Hh // ws) * (Ww // ws)
     Q = qkv.to("cuda", dt).contiguous()
     O = torch.full((B, L, C), float("nan"), device="cuda").to(dt)
@@ -98,7 +72,7 @@ def test_window12_walk_of_many_windows(ops, dt):
     qkv = bf16_round(gen((B, L, 3 * C), 11))
     do = bf16_round(gen((B, L, C), 12))
     bias = gen((H, N, N), 13, 0.5)
-    o, mask, dq_ref, db_ref = torch_window_attention(qkv, do, bias, B, Hh, Ww, ws, shift, H, hd)
+    o, mask, dq_ref, db_ref = torch_window_attention(qkv, do, bias, B, Hh, Ww, ws, shift, H, hd)[:4]
     Bw = B * (Hh // ws) * (Ww // ws)
     Q = qkv.to("cuda", dt).contiguous()
     O = torch.empty((B, L, C), device="cuda", dtype=dt)
