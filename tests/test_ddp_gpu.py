@@ -221,7 +221,7 @@ def test_bench_two_rank_line_on_one_gpu_over_gloo():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--dist-backend", "gloo", "--single-device", "--steps", "2", "--warmup", "1",
-           "--arch", "dino_vits16", "--img", "32", "--batch", "64", "--no-cpu-baseline", "--no-parity"]
+           "--arch", "dino_vits16", "--img", "32", "--batch", "64", "--full", "--no-cpu-baseline", "--no-parity"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

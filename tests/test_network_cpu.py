@@ -74,6 +74,25 @@ def test_bench_parent_launches_ranks_without_touching_the_gpu(monkeypatch):
     assert calls["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_extras_run_only_under_full(monkeypatch):
+    """A plain `bench.py` run skips every leg beside the headline figure; `--full` turns them all on, and the --no-*
+    options and --lean narrow it as before."""
+    import sys
+    import bench
+    legs = ("no_parity", "no_alt", "no_configs", "no_dp_proxy", "no_fp32_rate", "no_cpu_baseline")
+
+    def parsed(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", *argv])
+        a = bench.parse()
+        return a.full, {k for k in legs if getattr(a, k)}
+
+    assert parsed() == (False, set(legs))
+    assert parsed("--no-cpu-baseline") == (False, set(legs))
+    assert parsed("--full") == (True, set())
+    assert parsed("--full", "--no-cpu-baseline", "--no-parity") == (True, {"no_cpu_baseline", "no_parity"})
+    assert parsed("--full", "--lean") == (True, set(legs) - {"no_cpu_baseline"})
+
+
 def test_bench_refuses_a_traffic_file_from_other_kernel_sources(tmp_path):
     """`roofline.traffic` comes from a committed PMC file; bench.py must quote it only when
     the file's kernel-source fingerprint equals that of the sources it runs (tools/pmc_traffic.py records it)."""

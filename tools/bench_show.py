@@ -1,4 +1,4 @@
-"""Print the interesting parts of a bench.py JSON line.  usage: python tools/bench_show.py <file>"""
+"""Print the interesting parts of a `bench.py --full` JSON line.  usage: python tools/bench_show.py <file>"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 for k in ['value', 'ms_per_step', 'step_mfma_frac', 'config', 'cls_only_last_block', 'parity_mode_rate', 'residual_alt', 'cpu_baseline']:

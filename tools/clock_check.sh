@@ -1,15 +1,16 @@
 #!/bin/bash
-# usage (on the GPU box): tools/clock_check.sh <tag>   -> gpurun_out/<tag>_clock.txt
+# usage (on an MI355X): tools/clock_check.sh <tag>   -> $PROF_OUT/<tag>_clock.txt
 # tools/clock_probe.py under rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES (no other trace domain):
 # method 2 (GRBM_GUI_ACTIVE / 8 / wall) next to method 1 (in-kernel stamps) on the same >= 10 ms dispatches.
 set -e
 tag=$1
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+O=${PROF_OUT:-prof_out}; mkdir -p "$R/$O"       # output folder, under the repository root
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/clk_$$
-rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d /tmp/clk_$$ -- python3 $R/tools/clock_probe.py ${2:-32} > $R/gpurun_out/${tag}_clock_probe.log 2>&1
+rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d /tmp/clk_$$ -- python3 $R/tools/clock_probe.py ${2:-32} > $R/$O/${tag}_clock_probe.log 2>&1
 cd $R
-python3 - /tmp/clk_$$ gpurun_out/${tag}_clock_probe.log > gpurun_out/${tag}_clock.txt <<'EOF'
+python3 - /tmp/clk_$$ $O/${tag}_clock_probe.log > $O/${tag}_clock.txt <<'EOF'
 import csv, glob, json, sys
 d, log = sys.argv[1], sys.argv[2]
 cc = glob.glob(d + "/**/*counter_collection.csv", recursive=True)[0]
@@ -41,4 +42,4 @@ for i, p in enumerate(probes):
           f"GRBM {c2:7.1f} MHz  ratio {c2 / p['clock_mhz_in_kernel']:.3f}  MFMA-busy {sorted(busy)[1] * 100:5.1f} %")
 EOF
 rm -rf /tmp/clk_$$
-cat gpurun_out/${tag}_clock.txt
+cat $O/${tag}_clock.txt

@@ -1,9 +1,9 @@
 #!/bin/bash
 # usage (here, after tools/refresh_profiles.sh ran on the GPU box): tools/collect_profiles.sh [tag]
-# copies the judged summaries from gpurun_out/ (scratch) into profiles/ (tracked)
+# copies the judged summaries from $PROF_OUT/ (scratch) into profiles/ (tracked)
 set +e
 T=${1:-r04}
-G=gpurun_out
+G=${PROF_OUT:-prof_out}
 P=profiles
 cp $G/${T}_bench_n1*.json $P/
 cp $G/${T}_vitb.txt $P/${T}_rocprofv3_summary.txt
