@@ -5,25 +5,11 @@ Shapes: cait_S24_224's (N = 196, H = 8, hd = 48) and ragged ones (N = 100: a las
 import pytest
 import torch
 
+from cait_util import reference
 from util import assert_close, cosine
 
 pytestmark = pytest.mark.gpu
 bt = torch.bfloat16
-
-
-def reference(qkv, Wl, bl, Ww, bw, dO, scale):
-    """models/cait.py:111-128 in fp32 on the bf16-rounded operands; returns O and every gradient."""
-    B, N, _, H, hd = qkv.shape
-    x = qkv.float().clone().requires_grad_(True)
-    Wl, bl, Ww, bw = (t.clone().requires_grad_(True) for t in (Wl, bl, Ww, bw))
-    q, k, v = x[:, :, 0].permute(0, 2, 1, 3) * scale, x[:, :, 1].permute(0, 2, 1, 3), x[:, :, 2].permute(0, 2, 1, 3)
-    attn = q @ k.transpose(-2, -1)                                   # [B,H,N,N]
-    attn = (attn.permute(0, 2, 3, 1) @ Wl.t() + bl).permute(0, 3, 1, 2)
-    attn = attn.softmax(dim=-1)
-    attn = (attn.permute(0, 2, 3, 1) @ Ww.t() + bw).permute(0, 3, 1, 2)
-    out = (attn @ v).transpose(1, 2).reshape(B, N, H * hd)
-    out.backward(dO.float().reshape(B, N, H * hd))
-    return out.detach(), x.grad, Wl.grad, bl.grad, Ww.grad, bw.grad
 
 
 def make(B, N, seed=0, H=8, hd=48):
@@ -85,17 +71,20 @@ def test_unsupported_shapes_are_refused_and_fall_back():
     assert not O_.th_attn_supported(bt, 8, 197, 48)
 
 
-def test_cait_engine_fused_and_three_call_forms_agree(monkeypatch):
+@pytest.mark.parametrize("batch", ["3", "walk"])
+def test_cait_engine_fused_and_three_call_forms_agree(monkeypatch, batch):
     """cait_S24-shaped blocks (H = 8, hd = 48, N = 196) through the whole engine: the fused attention against the
-    three-call form, same weights and batch: logits, loss and every gradient."""
+    three-call form, same weights and batch: logits, loss and every gradient.  "walk": the smallest batch at which the
+    fused forward's workgroups walk 2 query blocks (74 on 256 CUs: walks of 2, 2, 2 and 1 blocks per image)."""
     from functools import partial
     import torch.nn as nn
     from oracle.vit_ref import seeded_init_
     from vit_torch_amd import CrossEntropyLoss, cait_models
     cfg = dict(img_size=224, patch_size=16, embed_dim=384, depth=2, num_heads=8, mlp_ratio=4, qkv_bias=True,
                norm_layer=partial(nn.LayerNorm, eps=1e-6), init_scale=1e-1, depth_token_only=1, num_classes=10)
+    B = 3 if batch == "3" else -(-2 * torch.cuda.get_device_properties(0).multi_processor_count // 7)
     g = torch.Generator("cpu").manual_seed(3)
-    x, y = torch.randn(3, 3, 224, 224, generator=g).cuda(), torch.randint(0, 10, (3,), generator=g).cuda()
+    x, y = torch.randn(B, 3, 224, 224, generator=g).cuda(), torch.randint(0, 10, (B,), generator=g).cuda()
     res = {}
     for form in ("1", "0"):
         monkeypatch.setenv("VITMI_TH_FUSED", form)
