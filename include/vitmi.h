@@ -237,9 +237,13 @@ int vitmi_attn_bwd(const void* qkv, const void* out, const void* dout,
 
 /* ------------------------------------------------------------- CaiT ops --
  * Talking-heads softmax (models/cait.py:118-122) on score tensors [B,H,N,ld] (row length
- * Nk <= 256 valid columns, H <= 8):  S' = Wl S + bl over the head axis, P = softmax_j(S'),
- * Pm = Ww P + bw.  P is kept for backward.  The q k^T, P v products around it are batched
- * vitmi_gemm calls that read q/k/v in place from the qkv tensor. */
+ * Nk <= 1024 valid columns, H <= 16; other shapes fail with VITMI_E_SHAPE before any launch):
+ * S' = Wl S + bl over the head axis, P = softmax_j(S'), Pm = Ww P + bw.  P is kept for backward.
+ * The q k^T, P v products around it are batched vitmi_gemm calls that read q/k/v in place from
+ * the qkv tensor.  Rows with H <= 8 and Nk <= 256 run one wave per row (as before the long form
+ * existed); longer rows or more heads run one workgroup per row with the row of all heads in LDS
+ * (CaiT at 384 / 448 pixels: 576 / 784 keys, up to 16 heads).  Columns Nk..ld-1 are neither
+ * read nor written by the long form. */
 int vitmi_th_softmax_fwd(const void* S, const float* Wl, const float* bl, const float* Ww,
                          const float* bw, void* P, void* Pm, int dtype,
                          int64_t B, int64_t H, int64_t N, int64_t Nk, int64_t ld, void* stream);
@@ -268,7 +272,8 @@ int vitmi_th_attn_bwd(const void* qkv, const void* dout, const float* Wl, const 
 
 /* Class attention core (models/cait.py:44-52): one query per image (the projected CLS
  * token, q [B, H*hd]) against k/v rows [B, N, .] with token stride kv_token_stride
- * (elements); out [B, H*hd]; p_save [B,H,N] fp32 (softmax, kept for backward). */
+ * (elements); out [B, H*hd]; p_save [B,H,N] fp32 (softmax, kept for backward).  hd <= 64 and
+ * N <= 1025 (CaiT at 448 pixels: 784 patches + CLS); rows over 256 tokens take the long forms. */
 int vitmi_class_attn_fwd(const void* q, const void* k, const void* v, int64_t kv_token_stride,
                          void* out, float* p_save, int dtype,
                          int64_t B, int64_t H, int64_t N, int64_t hd, float scale, void* stream);

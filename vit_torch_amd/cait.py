@@ -160,14 +160,6 @@ class CaitEngine(Engine):
         # talking-heads attention as one fused op where the shape allows (VITMI_TH_FUSED=0: the three-call form, for A/B)
         self.fused_th = os.environ.get("VITMI_TH_FUSED", "1") != "0"
 
-    # batched per-(image, head) products on the qkv tensor [B, Np, 3, H, hd] and on the score
-    # tensors [B, H, Np, NS]
-    def _scores(self, qkv, S, B, Np, H, hd, NS, scale):
-        D3 = 3 * H * hd
-        ops.gemm_batched(qkv, qkv, S, M=Np, N=Np, K=hd, lda=D3, ldb=D3, ldc=NS, a_kmajor=True, b_kmajor=True,
-                         batch=B * H, batch_inner=H, a_bs=(Np * D3, hd), b_bs=(Np * D3, hd),
-                         c_bs=(H * Np * NS, Np * NS), b_off=H * hd, alpha=scale)
-
     # ---------------------------------------------------------------- forward ---
     def forward(self, x, save: bool):
         m, T, R, pk = self.model, self.T, self.R, self.pack
@@ -201,7 +193,15 @@ class CaitEngine(Engine):
                    bias=pk.f32(conv.bias) if conv.bias is not None else None,
                    pos=pk.f32(m.pos_embed).view(Np, D), n_tok=Np)
         trunk = []
-        fused_th = self.fused_th and T == torch.bfloat16 and ops.th_attn_supported(T, H, Np, hd)
+        # talking-heads attention, in order of preference: the fused op; for bf16 rows the three-call form's kernels
+        # refuse as they stood before the long form (H > 8 or N > 256), the long op, which keeps nothing quadratic for the
+        # backward; else the three-call form, whose score tensors S, P, P' are kept (the parity modes: small batches)
+        if self.fused_th and T == torch.bfloat16 and ops.th_attn_supported(T, H, Np, hd):
+            th_mode = "fused"
+        elif self.fused_th and (H > 8 or Np > 256) and ops.th_long_supported(T, H, Np, hd):
+            th_mode = "long"
+        else:
+            th_mode = "three"
         for blk in m.blocks:
             a, mlp = blk.attn, blk.mlp
             ln1, mean1, rstd1 = new(M, D, T), vec(M), vec(M)
@@ -211,21 +211,21 @@ class CaitEngine(Engine):
             self._gemm(ln1, self._w(a.qkv.weight), qkv, bias=pk.f32(a.qkv.bias) if a.qkv.bias is not None else None)
             O = new(M, D, T)
             D3 = 3 * D
-            if fused_th:
+            if th_mode == "fused":
                 # ONE op: the score rows stay in LDS, both head mixes run on the matrix pipe, nothing but O is kept
                 # (cait_fused.hip; the backward recomputes the scores from q, k)
                 ops.th_attn_fwd(qkv, pk.f32(a.proj_l.weight), pk.f32(a.proj_l.bias), pk.f32(a.proj_w.weight),
                                 pk.f32(a.proj_w.bias), O, B, H, Np, hd, a.scale)
                 S = P = Pm = None
+            elif th_mode == "long":
+                # the three-call kernels with the score tensors dropped here and recomputed by the backward
+                ops.th_long_fwd(qkv, pk.f32(a.proj_l.weight), pk.f32(a.proj_l.bias), pk.f32(a.proj_w.weight),
+                                pk.f32(a.proj_w.bias), O, B, H, Np, hd, a.scale)
+                S = P = Pm = None
             else:
-                S = torch.empty((B, H, Np, NS), dtype=T, device=dev)
-                self._scores(qkv, S, B, Np, H, hd, NS, a.scale)
-                P, Pm = torch.empty_like(S), torch.empty_like(S)
-                ops.th_softmax_fwd(S, pk.f32(a.proj_l.weight), pk.f32(a.proj_l.bias), pk.f32(a.proj_w.weight),
-                                   pk.f32(a.proj_w.bias), P, Pm, B, H, Np, Np, NS)
-                ops.gemm_batched(Pm, qkv, O, M=Np, N=hd, K=Np, lda=NS, ldb=D3, ldc=D, a_kmajor=True, b_kmajor=False,
-                                 batch=B * H, batch_inner=H, a_bs=(H * Np * NS, Np * NS), b_bs=(Np * D3, hd),
-                                 c_bs=(Np * D, hd), b_off=2 * D)
+                S, P, Pm = ops.th_three_call_fwd(qkv, pk.f32(a.proj_l.weight), pk.f32(a.proj_l.bias),
+                                                 pk.f32(a.proj_w.weight), pk.f32(a.proj_w.bias), O, B, H, Np, hd,
+                                                 a.scale, NS)
             X1, f1 = new(M, D, R), new(M, D, T)
             self._gemm(O, self._w(a.proj.weight), X1, epilogue=EPI_RESIDUAL, bias=pk.f32(a.proj.bias), R=X,
                        gamma=pk.f32(blk.gamma_1), C2=f1)
@@ -282,7 +282,7 @@ class CaitEngine(Engine):
         ops.layernorm_fwd(Cx, pk.f32(m.norm.weight), pk.f32(m.norm.bias), feat, meanf, rstdf, m.norm.eps, M=B, D=D)
         out, head_saved = head_forward(pk, self.head, feat)
         if save:
-            self.saved = dict(B=B, Np=Np, D=D, H=H, hd=hd, Kp=Kp, NS=NS, patches=patches, trunk=trunk, ca=ca,
+            self.saved = dict(B=B, Np=Np, D=D, H=H, hd=hd, Kp=Kp, NS=NS, th_mode=th_mode, patches=patches, trunk=trunk, ca=ca,
                               Cf=Cx, meanf=meanf, rstdf=rstdf, head=head_saved)
         return out
 
@@ -387,7 +387,11 @@ class CaitEngine(Engine):
             self._gemm(Gb, O, pk.g(a.proj.weight), a_kmajor=False, b_kmajor=False)
             # talking-heads attention backward
             dqkv = new(M, D3, T)
-            if S is None:
+            if s["th_mode"] == "long":
+                ops.th_long_bwd(qkv, dO, pk.f32(a.proj_l.weight), pk.f32(a.proj_l.bias), pk.f32(a.proj_w.weight),
+                                pk.f32(a.proj_w.bias), dqkv, pk.g(a.proj_l.weight), pk.g(a.proj_l.bias),
+                                pk.g(a.proj_w.weight), pk.g(a.proj_w.bias), B, H, Np, hd, a.scale)
+            elif S is None:
                 # fused form: the scores are recomputed inside the row kernel, which also forms dP' = dO v^T, runs the softmax
                 # backward through both mixes and writes the four mixing-parameter gradients; dS and P' (scratch here) go
                 # through HBM once to the products kernel, which writes dQ, dK and dV
@@ -398,24 +402,9 @@ class CaitEngine(Engine):
                                 pk.f32(a.proj_w.bias), dqkv, dS, Pm, NSb, pk.g(a.proj_l.weight), pk.g(a.proj_l.bias),
                                 pk.g(a.proj_w.weight), pk.g(a.proj_w.bias), B, H, Np, hd, a.scale)
             else:
-                dPm = torch.empty_like(S)
-                ops.gemm_batched(dO, qkv, dPm, M=Np, N=Np, K=hd, lda=D, ldb=D3, ldc=NS, a_kmajor=True, b_kmajor=True,
-                                 batch=B * H, batch_inner=H, a_bs=(Np * D, hd), b_bs=(Np * D3, hd),
-                                 c_bs=(H * Np * NS, Np * NS), b_off=2 * D)
-                dS = torch.empty_like(S)
-                ops.th_softmax_bwd(S, P, dPm, pk.f32(a.proj_l.weight), pk.f32(a.proj_w.weight), dS,
-                                   pk.g(a.proj_l.weight), pk.g(a.proj_l.bias), pk.g(a.proj_w.weight),
-                                   pk.g(a.proj_w.bias), B, H, Np, Np, NS)
-                ops.gemm_batched(dS, qkv, dqkv, M=Np, N=hd, K=Np, lda=NS, ldb=D3, ldc=D3, a_kmajor=True, b_kmajor=False,
-                                 batch=B * H, batch_inner=H, a_bs=(H * Np * NS, Np * NS), b_bs=(Np * D3, hd),
-                                 c_bs=(Np * D3, hd), b_off=D, alpha=a.scale)                          # dQ = scale dS K
-            if S is not None:            # three-call form: the two products that contract over the queries
-                ops.gemm_batched(Pm, dO, dqkv, M=Np, N=hd, K=Np, lda=NS, ldb=D, ldc=D3, a_kmajor=False, b_kmajor=False,
-                                 batch=B * H, batch_inner=H, a_bs=(H * Np * NS, Np * NS), b_bs=(Np * D, hd),
-                                 c_bs=(Np * D3, hd), c_off=2 * D)                                   # dV = P'^T dO
-                ops.gemm_batched(dS, qkv, dqkv, M=Np, N=hd, K=Np, lda=NS, ldb=D3, ldc=D3, a_kmajor=False, b_kmajor=False,
-                                 batch=B * H, batch_inner=H, a_bs=(H * Np * NS, Np * NS), b_bs=(Np * D3, hd),
-                                 c_bs=(Np * D3, hd), c_off=D, alpha=a.scale)                          # dK = scale dS^T Q
+                ops.th_three_call_bwd(qkv, dO, S, P, Pm, pk.f32(a.proj_l.weight), pk.f32(a.proj_w.weight), dqkv,
+                                      pk.g(a.proj_l.weight), pk.g(a.proj_l.bias), pk.g(a.proj_w.weight),
+                                      pk.g(a.proj_w.bias), B, H, Np, hd, a.scale, NS)
             dln1 = new(M, D, T)
             self._gemm(dqkv, self._w(a.qkv.weight), dln1, b_kmajor=False)
             self._gemm(dqkv, ln1, pk.g(a.qkv.weight), a_kmajor=False, b_kmajor=False)

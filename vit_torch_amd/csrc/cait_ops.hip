@@ -7,7 +7,8 @@
 //    tokens, one wave per (image, head);
 //  * column sum of an element-wise product (LayerScale gradient).
 // Correctness-first versions: the score tensors S, P, P' live in HBM between the batched
-// MFMA products (gemm.hip, batched form) and these kernels.  H <= 8, row length <= 256.
+// MFMA products (gemm.hip, batched form) and these kernels.  H <= 8 and rows of <= 256 keys run one
+// wave per row; up to 16 heads and 1024 keys (CaiT at 384 / 448 pixels) one workgroup per row ("long rows" below).
 #include <atomic>
 #include "common.h"
 
@@ -438,9 +439,219 @@ inline int th_bwd_blocks(int64_t rows) {
                                         // register bound lowered to three / four waves per SIMD measured slower: 86 / 99 vs 71 us)
 }
 
+// ---- long rows: H <= 16 heads, rows of up to 1024 keys (CaiT at 384 / 448 pixels: 576 / 784 patch tokens).  The
+// wave-per-row kernels above keep a row of all heads in registers, which no longer fits; here ONE WORKGROUP walks a row,
+// the row of all heads sits in LDS (fp32, [head][key] at an odd pitch, so the per-pair walks below hit distinct banks),
+// a thread owns keys tid, tid + 256, ... for the head mixes and the softmax, and the row statistics are block reductions
+// in a fixed order.  HM = 8 or 16 heads in straight-line code (surplus heads are zero rows of weights and scores).
+constexpr int TH_LONG_MAXH = 16;
+constexpr int TH_LONG_MAXC = 1024;
+__host__ __device__ constexpr int th_long_pitch(int Nk) { return Nk | 1; }
+
+template <int HM>
+__device__ __forceinline__ void th_long_weights(const float* W, const float* bias, float* w_s, float* b_s, int H) {
+  const int t = threadIdx.x;
+  if (t < HM * HM) {
+    const int a = t / HM, c = t % HM;
+    w_s[t] = (a < H && c < H) ? W[a * H + c] : 0.f;
+  }
+  if (t < HM) b_s[t] = t < H ? bias[t] : 0.f;
+}
+
+// v[h] over the workgroup: every wave folds its lanes (butterfly), then the four wave totals in a fixed order; red is
+// [4][HM] and free again when this returns
+template <int HM, bool MAX>
+__device__ __forceinline__ void th_long_block_reduce(float (&v)[HM], float* red) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int h = 0; h < HM; ++h) {
+    const float x = MAX ? wave_max(v[h]) : wave_sum(v[h]);
+    if (lane == 0) red[w * HM + h] = x;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int h = 0; h < HM; ++h)
+    v[h] = MAX ? fmaxf(fmaxf(red[h], red[HM + h]), fmaxf(red[2 * HM + h], red[3 * HM + h]))
+               : (red[h] + red[HM + h]) + (red[2 * HM + h] + red[3 * HM + h]);
+  __syncthreads();
+}
+
+template <typename T, int HM>
+__global__ __launch_bounds__(256) void th_long_softmax_fwd_kernel(const T* __restrict__ S, const float* __restrict__ Wl,
+                                                                  const float* __restrict__ bl, const float* __restrict__ Ww,
+                                                                  const float* __restrict__ bw, T* __restrict__ P,
+                                                                  T* __restrict__ Pm, int H, int N, int Nk, int ld) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];     // [HM][pitch]: S', then exp(S' - max)
+  __shared__ float wl[HM * HM], ww[HM * HM], blv[HM], bwv[HM], red[4 * HM];
+  const int tid = threadIdx.x, pitch = th_long_pitch(Nk);
+  const int64_t row = blockIdx.x, b = row / N, i = row % N;
+  constexpr bool FAST = sizeof(T) == 2;                          // as th_softmax_fwd_kernel
+  th_long_weights<HM>(Wl, bl, wl, blv, H);
+  th_long_weights<HM>(Ww, bw, ww, bwv, H);
+  __syncthreads();
+  float m[HM];
+#pragma unroll
+  for (int h = 0; h < HM; ++h) m[h] = -INFINITY;
+  for (int j = tid; j < Nk; j += 256) {
+    float s[HM];
+#pragma unroll
+    for (int h = 0; h < HM; ++h) s[h] = h < H ? to_f32(S[((b * H + h) * N + i) * ld + j]) : 0.f;
+#pragma unroll
+    for (int hp = 0; hp < HM; ++hp) {
+      float a = blv[hp];
+#pragma unroll
+      for (int h = 0; h < HM; ++h) a = fmaf(wl[hp * HM + h], s[h], a);
+      sm[hp * pitch + j] = a;
+      m[hp] = fmaxf(m[hp], a);
+    }
+  }
+  th_long_block_reduce<HM, true>(m, red);
+  float l[HM];
+#pragma unroll
+  for (int h = 0; h < HM; ++h) l[h] = 0.f;
+  for (int j = tid; j < Nk; j += 256) {
+#pragma unroll
+    for (int hp = 0; hp < HM; ++hp) {
+      const float x = sm[hp * pitch + j] - m[hp];
+      const float e = FAST ? __builtin_amdgcn_exp2f(x * 1.4426950408889634f) : expf(x);
+      sm[hp * pitch + j] = e;
+      l[hp] += e;
+    }
+  }
+  th_long_block_reduce<HM, false>(l, red);
+#pragma unroll
+  for (int h = 0; h < HM; ++h) l[h] = FAST ? __builtin_amdgcn_rcpf(l[h]) : 1.f / l[h];
+  for (int j = tid; j < Nk; j += 256) {
+    float p[HM];
+#pragma unroll
+    for (int hp = 0; hp < HM; ++hp) {
+      const T pv = from_f32<T>(sm[hp * pitch + j] * l[hp]);
+      p[hp] = to_f32(pv);                                        // the mix and the backward see the STORED probabilities
+      if (hp < H) P[((b * H + hp) * N + i) * ld + j] = pv;
+    }
+#pragma unroll
+    for (int ho = 0; ho < HM; ++ho) {
+      float a = bwv[ho];
+#pragma unroll
+      for (int hp = 0; hp < HM; ++hp) a = fmaf(ww[ho * HM + hp], p[hp], a);
+      if (ho < H) Pm[((b * H + ho) * N + i) * ld + j] = from_f32<T>(a);
+    }
+  }
+}
+
+// Backward, a grid-stride walk of rows by th_bwd_blocks(rows) workgroups, each writing ONE partial row of the parameter
+// gradients ([dWl | dbl | dWw | dbw] as th_softmax_bwd_kernel).  Per row, two LDS planes A and B:
+//   A = P, B = dP'                 -> dWw / dbw partials; B := dP = Ww^T dP' (per key), the row dots sum_j dP P
+//   A := dS' = P (dP - dot), B := S -> dWl / dbl partials; dS = Wl^T dS' to HBM
+// A parameter-gradient entry (a, c) is owned by the threads tid % HM^2 == a HM + c, which split the keys into
+// 256 / HM^2 interleaved slices; the slices fold in a fixed order at the end.
+template <typename T, int HM>
+__global__ __launch_bounds__(256) void th_long_softmax_bwd_kernel(const T* __restrict__ S, const T* __restrict__ P,
+                                                                  const T* __restrict__ dPm, const float* __restrict__ Wl,
+                                                                  const float* __restrict__ Ww, T* __restrict__ dS,
+                                                                  float* __restrict__ part, int64_t rows, int H, int N,
+                                                                  int Nk, int ld) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];     // A [HM][pitch] | B [HM][pitch]
+  __shared__ float wl[HM * HM], ww[HM * HM], dummy[HM], red[4 * HM];
+  constexpr int NP = HM * HM, SL = 256 / NP;
+  const int tid = threadIdx.x, pitch = th_long_pitch(Nk);
+  const int pa = (tid % NP) / HM, pc = tid % HM, slice = tid / NP;
+  float* A = sm;
+  float* Bp = sm + HM * pitch;
+  th_long_weights<HM>(Wl, Wl, wl, dummy, H);
+  th_long_weights<HM>(Ww, Ww, ww, dummy, H);
+  float gWl = 0.f, gWw = 0.f, gbl = 0.f, gbw = 0.f;
+  for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+    const int64_t b = row / N, i = row % N;
+    __syncthreads();                                             // the previous row's planes (and the weights) are done
+    for (int j = tid; j < Nk; j += 256) {
+#pragma unroll
+      for (int h = 0; h < HM; ++h) {
+        const int64_t o = ((b * H + (h < H ? h : 0)) * N + i) * ld + j;
+        A[h * pitch + j] = h < H ? to_f32(P[o]) : 0.f;
+        Bp[h * pitch + j] = h < H ? to_f32(dPm[o]) : 0.f;
+      }
+    }
+    __syncthreads();
+    for (int j = slice; j < Nk; j += SL) {                       // dWw[a][c] += dP'[a] P[c];  dbw[a] += dP'[a]
+      const float g = Bp[pa * pitch + j];
+      gWw = fmaf(g, A[pc * pitch + j], gWw);
+      gbw += g;
+    }
+    __syncthreads();
+    float dot[HM];
+#pragma unroll
+    for (int h = 0; h < HM; ++h) dot[h] = 0.f;
+    for (int j = tid; j < Nk; j += 256) {
+      float g[HM];
+#pragma unroll
+      for (int h = 0; h < HM; ++h) g[h] = Bp[h * pitch + j];
+#pragma unroll
+      for (int hp = 0; hp < HM; ++hp) {
+        float a = 0.f;
+#pragma unroll
+        for (int ho = 0; ho < HM; ++ho) a = fmaf(ww[ho * HM + hp], g[ho], a);
+        Bp[hp * pitch + j] = a;
+        dot[hp] = fmaf(a, A[hp * pitch + j], dot[hp]);
+      }
+    }
+    th_long_block_reduce<HM, false>(dot, red);
+    for (int j = tid; j < Nk; j += 256) {
+#pragma unroll
+      for (int h = 0; h < HM; ++h) {
+        const float p = A[h * pitch + j];
+        A[h * pitch + j] = p * (Bp[h * pitch + j] - dot[h]);
+        Bp[h * pitch + j] = h < H ? to_f32(S[((b * H + h) * N + i) * ld + j]) : 0.f;
+      }
+    }
+    __syncthreads();
+    for (int j = slice; j < Nk; j += SL) {                       // dWl[a][c] += dS'[a] S[c];  dbl[a] += dS'[a]
+      const float d = A[pa * pitch + j];
+      gWl = fmaf(d, Bp[pc * pitch + j], gWl);
+      gbl += d;
+    }
+    for (int j = tid; j < Nk; j += 256) {
+      float d[HM];
+#pragma unroll
+      for (int h = 0; h < HM; ++h) d[h] = A[h * pitch + j];
+#pragma unroll
+      for (int h = 0; h < HM; ++h) {
+        float a = 0.f;
+#pragma unroll
+        for (int hp = 0; hp < HM; ++hp) a = fmaf(wl[hp * HM + h], d[hp], a);
+        if (h < H) dS[((b * H + h) * N + i) * ld + j] = from_f32<T>(a);
+      }
+    }
+  }
+  // fold the key slices in order: slot s of each quantity holds slice s
+  __syncthreads();
+  float* f = sm;                                                 // 4 x 256 floats (the planes hold at least 2 x 8 x 17)
+  f[tid] = gWl; f[256 + tid] = gbl; f[512 + tid] = gWw; f[768 + tid] = gbw;
+  __syncthreads();
+  if (tid < NP) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+    for (int s = 0; s < SL; ++s) {
+      s0 += f[s * NP + tid]; s1 += f[256 + s * NP + tid]; s2 += f[512 + s * NP + tid]; s3 += f[768 + s * NP + tid];
+    }
+    float* prow = part + (int64_t)blockIdx.x * (2 * H * H + 2 * H);
+    if (pa < H && pc < H) {
+      prow[pa * H + pc] = s0;
+      prow[H * H + H + pa * H + pc] = s2;
+      if (pc == 0) { prow[H * H + pa] = s1; prow[2 * H * H + H + pa] = s3; }
+    }
+  }
+}
+
+// the long forms: class attention over up to 1025 tokens (CaiT at 448 pixels: 784 patches + CLS).  The generic forward
+// keeps CA_LONG_MAXC keys per lane, the vector kernels CA_LONG_STEPS steps of 8 rows (whole batches of 8 steps)
+constexpr int CA_MAXN_LONG = 1025;
+constexpr int CA_LONG_MAXC = (CA_MAXN_LONG + 63) / 64;
+constexpr int CA_LONG_STEPS = ((CA_MAXN_LONG + 7) / 8 + 7) / 8 * 8;
+
 // ---- class attention: one wave per (b, h); q [B, H*hd] (already scaled by the caller via
 // `scale`), k/v rows at token stride ts, p_save [B,H,N] fp32
-template <typename T>
+template <typename T, int MAXC>
 __global__ __launch_bounds__(256) void class_attn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                             const T* __restrict__ v, int64_t ts, T* __restrict__ out,
                                                             float* __restrict__ psave, int64_t BH, int H, int N,
@@ -451,9 +662,9 @@ __global__ __launch_bounds__(256) void class_attn_fwd_kernel(const T* __restrict
   const int64_t b = bh / H;
   const int h = (int)(bh % H);
   const T* qv = q + b * H * hd + h * hd;
-  float sc[TH_MAXC], mx = -INFINITY;
+  float sc[MAXC], mx = -INFINITY;
 #pragma unroll
-  for (int c = 0; c < TH_MAXC; ++c) {
+  for (int c = 0; c < MAXC; ++c) {
     const int j = c * 64 + lane;
     float a = -INFINITY;
     if (j < N) {
@@ -467,10 +678,10 @@ __global__ __launch_bounds__(256) void class_attn_fwd_kernel(const T* __restrict
   mx = wave_max(mx);
   float sum = 0.f;
 #pragma unroll
-  for (int c = 0; c < TH_MAXC; ++c) { sc[c] = expf(sc[c] - mx); sum += sc[c]; }
+  for (int c = 0; c < MAXC; ++c) { sc[c] = expf(sc[c] - mx); sum += sc[c]; }
   sum = wave_sum(sum);
 #pragma unroll
-  for (int c = 0; c < TH_MAXC; ++c) {
+  for (int c = 0; c < MAXC; ++c) {
     sc[c] /= sum;
     const int j = c * 64 + lane;
     if (j < N) psave[bh * N + j] = sc[c];
@@ -479,7 +690,7 @@ __global__ __launch_bounds__(256) void class_attn_fwd_kernel(const T* __restrict
   float acc = 0.f;
   const int dl = lane < hd ? lane : 0;
 #pragma unroll
-  for (int c = 0; c < TH_MAXC; ++c)
+  for (int c = 0; c < MAXC; ++c)
     for (int jj = 0; jj < 64; ++jj) {
       const int j = c * 64 + jj;
       if (j >= N) break;
@@ -489,7 +700,7 @@ __global__ __launch_bounds__(256) void class_attn_fwd_kernel(const T* __restrict
 }
 
 // backward: dq [B,H*hd] (fp32), dk/dv rows [B,N,*] at stride ts
-template <typename T>
+template <typename T, int MAXC>
 __global__ __launch_bounds__(256) void class_attn_bwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                             const T* __restrict__ v, int64_t ts,
                                                             const T* __restrict__ dout, const float* __restrict__ psave,
@@ -503,9 +714,9 @@ __global__ __launch_bounds__(256) void class_attn_bwd_kernel(const T* __restrict
   const T* qv = q + b * H * hd + h * hd;
   const T* dov = dout + b * H * hd + h * hd;
   // dp_j = dout . v_j ; ds_j = p_j (dp_j - sum p dp)
-  float p[TH_MAXC], ds[TH_MAXC], dot = 0.f;
+  float p[MAXC], ds[MAXC], dot = 0.f;
 #pragma unroll
-  for (int c = 0; c < TH_MAXC; ++c) {
+  for (int c = 0; c < MAXC; ++c) {
     const int j = c * 64 + lane;
     p[c] = 0.f; ds[c] = 0.f;
     if (j < N) {
@@ -519,10 +730,10 @@ __global__ __launch_bounds__(256) void class_attn_bwd_kernel(const T* __restrict
   }
   dot = wave_sum(dot);
 #pragma unroll
-  for (int c = 0; c < TH_MAXC; ++c) ds[c] = p[c] * (ds[c] - dot);
+  for (int c = 0; c < MAXC; ++c) ds[c] = p[c] * (ds[c] - dot);
   // dv_j = p_j dout ; dk_j = ds_j * scale * q   (rows written by the lane that owns key j)
 #pragma unroll
-  for (int c = 0; c < TH_MAXC; ++c) {
+  for (int c = 0; c < MAXC; ++c) {
     const int j = c * 64 + lane;
     if (j < N) {
       T* dvr = dv + (b * N + j) * dts + h * hd;
@@ -537,12 +748,64 @@ __global__ __launch_bounds__(256) void class_attn_bwd_kernel(const T* __restrict
   float acc = 0.f;
   const int dl = lane < hd ? lane : 0;
 #pragma unroll
-  for (int c = 0; c < TH_MAXC; ++c)
+  for (int c = 0; c < MAXC; ++c)
     for (int jj = 0; jj < 64; ++jj) {
       const int j = c * 64 + jj;
       if (j >= N) break;
       acc = fmaf(__shfl(ds[c], jj), to_f32(k[(b * N + j) * ts + h * hd + dl]), acc);
     }
+  if (lane < hd) dq[b * H * hd + h * hd + lane] = from_f32<T>(acc * scale);
+}
+
+// the same backward for rows longer than 64 * TH_MAXC: the keys are walked 64 at a time, twice (the row dot first, then
+// the gradients, recomputing dout . v_j), so no per-key array has to live in registers across the walk
+template <typename T>
+__global__ __launch_bounds__(256) void class_attn_bwd_long_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                                 const T* __restrict__ v, int64_t ts,
+                                                                 const T* __restrict__ dout, const float* __restrict__ psave,
+                                                                 T* __restrict__ dq, T* __restrict__ dk, T* __restrict__ dv,
+                                                                 int64_t dts, int64_t BH, int H, int N, int hd, float scale) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t bh = (int64_t)blockIdx.x * 4 + w;
+  if (bh >= BH) return;
+  const int64_t b = bh / H;
+  const int h = (int)(bh % H);
+  const T* qv = q + b * H * hd + h * hd;
+  const T* dov = dout + b * H * hd + h * hd;
+  auto dp_of = [&](int j) {
+    const T* vr = v + (b * N + j) * ts + h * hd;
+    float a = 0.f;
+    for (int d = 0; d < hd; ++d) a = fmaf(to_f32(dov[d]), to_f32(vr[d]), a);
+    return a;
+  };
+  float dot = 0.f;
+  for (int c = 0; c < CA_LONG_MAXC; ++c) {
+    const int j = c * 64 + lane;
+    if (j < N) dot = fmaf(psave[bh * N + j], dp_of(j), dot);
+  }
+  dot = wave_sum(dot);
+  float acc = 0.f;
+  const int dl = lane < hd ? lane : 0;
+  for (int c = 0; c < CA_LONG_MAXC; ++c) {
+    if (c * 64 >= N) break;
+    const int j = c * 64 + lane;
+    float ds = 0.f;
+    if (j < N) {
+      const float p = psave[bh * N + j];
+      ds = p * (dp_of(j) - dot);
+      T* dvr = dv + (b * N + j) * dts + h * hd;
+      T* dkr = dk + (b * N + j) * dts + h * hd;
+      for (int d = 0; d < hd; ++d) {
+        dvr[d] = from_f32<T>(p * to_f32(dov[d]));
+        dkr[d] = from_f32<T>(ds * scale * to_f32(qv[d]));
+      }
+    }
+    for (int jj = 0; jj < 64; ++jj) {
+      const int j2 = c * 64 + jj;
+      if (j2 >= N) break;
+      acc = fmaf(__shfl(ds, jj), to_f32(k[(b * N + j2) * ts + h * hd + dl]), acc);
+    }
+  }
   if (lane < hd) dq[b * H * hd + h * hd + lane] = from_f32<T>(acc * scale);
 }
 
@@ -564,6 +827,7 @@ __device__ __forceinline__ float ca_rows_sum(float a) {         // over the 8 ro
   a += __shfl_xor(a, 8, 64); a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
   return a;
 }
+template <int STEPS>
 __global__ __launch_bounds__(256) void class_attn_fwd_vec_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
                                                                 const bf16* __restrict__ v, int64_t ts, bf16* __restrict__ out,
                                                                 float* __restrict__ psave, int64_t BH, int H, int N, int hd, float scale) {
@@ -583,9 +847,9 @@ __global__ __launch_bounds__(256) void class_attn_fwd_vec_kernel(const bf16* __r
   const bf16* vb = v + b * N * ts + h * hd + pc * 8;
   // a batch = 8 steps whose 8 loads are issued together, unconditionally, from clamped rows (one round trip per batch: a
   // branch around each load would cost one per step); whole batches beyond N are skipped (wave-uniform)
-  float sc[CA_STEPS], mx = -INFINITY;
+  float sc[STEPS], mx = -INFINITY;
 #pragma unroll
-  for (int s0 = 0; s0 < CA_STEPS; s0 += 8) {
+  for (int s0 = 0; s0 < STEPS; s0 += 8) {
     ca_fence();                                                  // keep the batches apart (hipcc hoists all 32 loads otherwise)
     bf16x8 raw[8];
     if (s0 * 8 < N) {
@@ -611,14 +875,14 @@ __global__ __launch_bounds__(256) void class_attn_fwd_vec_kernel(const bf16* __r
   mx = fmaxf(mx, __shfl_xor(mx, 8, 64)); mx = fmaxf(mx, __shfl_xor(mx, 16, 64)); mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
   float sum = 0.f;
 #pragma unroll
-  for (int s = 0; s < CA_STEPS; ++s) { sc[s] = expf(sc[s] - mx); sum += sc[s]; }     // exp(-inf) = 0 for the padding
+  for (int s = 0; s < STEPS; ++s) { sc[s] = expf(sc[s] - mx); sum += sc[s]; }     // exp(-inf) = 0 for the padding
   sum = ca_rows_sum(sum);
   const float rs = 1.f / sum;
   float acc[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
 #pragma unroll
-  for (int s0 = 0; s0 < CA_STEPS; s0 += 8) {
+  for (int s0 = 0; s0 < STEPS; s0 += 8) {
     ca_fence();                                                  // keep the batches apart (hipcc hoists all 32 loads otherwise)
     if (s0 * 8 < N) {
       bf16x8 raw[8];
@@ -642,6 +906,7 @@ __global__ __launch_bounds__(256) void class_attn_fwd_vec_kernel(const bf16* __r
   if (rsub == 0 && pok) *reinterpret_cast<bf16x8*>(out + b * H * hd + h * hd + piece * 8) = o;
 }
 
+template <int STEPS>
 __global__ __launch_bounds__(256) void class_attn_bwd_vec_kernel(const bf16* __restrict__ q, const bf16* __restrict__ k,
                                                                 const bf16* __restrict__ v, int64_t ts,
                                                                 const bf16* __restrict__ dout, const float* __restrict__ psave,
@@ -663,9 +928,9 @@ __global__ __launch_bounds__(256) void class_attn_bwd_vec_kernel(const bf16* __r
   const bf16* kb = k + b * N * ts + h * hd + pc * 8;
   const bf16* vb = v + b * N * ts + h * hd + pc * 8;
   // dp_j = dout . v_j ; ds_j = p_j (dp_j - sum p dp)
-  float p[CA_STEPS], ds[CA_STEPS], dot = 0.f;
+  float p[STEPS], ds[STEPS], dot = 0.f;
 #pragma unroll
-  for (int s0 = 0; s0 < CA_STEPS; s0 += 8) {
+  for (int s0 = 0; s0 < STEPS; s0 += 8) {
     ca_fence();                                                  // keep the batches apart (hipcc hoists all 32 loads otherwise)
     bf16x8 raw[8];
     float pr[8];
@@ -699,7 +964,7 @@ __global__ __launch_bounds__(256) void class_attn_bwd_vec_kernel(const bf16* __r
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
 #pragma unroll
-  for (int s0 = 0; s0 < CA_STEPS; s0 += 8) {
+  for (int s0 = 0; s0 < STEPS; s0 += 8) {
     ca_fence();                                                  // keep the batches apart (hipcc hoists all 32 loads otherwise)
     if (s0 * 8 < N) {
       bf16x8 raw[8];
@@ -763,9 +1028,33 @@ inline int cm_splits(int64_t M) { int64_t s = (M + 3) / 4; return (int)(s < 512 
 }  // namespace
 
 static int th_check(int H, int Nk, int ld, const char* who) {
-  VITMI_REQUIRE(H >= 1 && H <= TH_MAXH, VITMI_E_SHAPE, "%s: %d heads, at most %d supported", who, H, TH_MAXH);
-  VITMI_REQUIRE(Nk >= 1 && Nk <= 64 * TH_MAXC && ld >= Nk, VITMI_E_SHAPE, "%s: row length %d not in [1, %d]", who, Nk, 64 * TH_MAXC);
+  VITMI_REQUIRE(H >= 1 && H <= TH_LONG_MAXH, VITMI_E_SHAPE, "%s: %d heads, at most %d supported", who, H, TH_LONG_MAXH);
+  VITMI_REQUIRE(Nk >= 1 && Nk <= TH_LONG_MAXC && ld >= Nk, VITMI_E_SHAPE, "%s: row length %d not in [1, %d]", who, Nk, TH_LONG_MAXC);
   return 0;
+}
+
+// the wave-per-row kernels take every shape they took before the long form existed; the rest goes to the long form
+static bool th_long(int H, int Nk) { return H > TH_MAXH || Nk > 64 * TH_MAXC; }
+static size_t th_long_lds(int H, int Nk, int planes) {
+  const size_t b = (size_t)planes * (H > 8 ? 16 : 8) * th_long_pitch(Nk) * sizeof(float);
+  return b > 4096 ? b : 4096;                      // the backward folds its 4 x 256 partials through the same LDS
+}
+
+static int th_long_fwd(const void* S, const float* Wl, const float* bl, const float* Ww, const float* bw, void* P, void* Pm,
+                       int dtype, int64_t B, int H, int N, int Nk, int ld, hipStream_t stream) {
+  const size_t lds = th_long_lds(H, Nk, 1);
+  const dim3 grid((unsigned)(B * N));
+  int rc = 0;
+#define TH_LFWD(T, HM)                                                                                                 \
+  do {                                                                                                                 \
+    if ((rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(th_long_softmax_fwd_kernel<T, HM>), (int)lds, "th_softmax_fwd"))) return rc; \
+    hipLaunchKernelGGL((th_long_softmax_fwd_kernel<T, HM>), grid, dim3(256), lds, stream, (const T*)S, Wl, bl, Ww, bw, (T*)P, (T*)Pm, H, N, Nk, ld); \
+  } while (0)
+  if (dtype == VITMI_BF16) { if (H > 8) TH_LFWD(bf16, 16); else TH_LFWD(bf16, 8); }
+  else if (dtype == VITMI_F32) { if (H > 8) TH_LFWD(float, 16); else TH_LFWD(float, 8); }
+  else return vitmi_fail(VITMI_E_DTYPE, "th_softmax_fwd: bad dtype");
+#undef TH_LFWD
+  return vitmi_check_launch("th_long_softmax_fwd_kernel");
 }
 
 extern "C" int vitmi_th_softmax_fwd(const void* S, const float* Wl, const float* bl, const float* Ww,
@@ -775,6 +1064,7 @@ extern "C" int vitmi_th_softmax_fwd(const void* S, const float* Wl, const float*
   int rc = th_check((int)H, (int)Nk, (int)ld, "th_softmax_fwd");
   if (rc) return rc;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  if (th_long((int)H, (int)Nk)) return th_long_fwd(S, Wl, bl, Ww, bw, P, Pm, dtype, B, (int)H, (int)N, (int)Nk, (int)ld, stream);
   const int64_t rows = B * N;
   dim3 grid((unsigned)((rows + 3) / 4));
   // four keys per lane as one vector when the rows allow it
@@ -807,15 +1097,29 @@ extern "C" int vitmi_th_softmax_bwd(const void* S, const void* P, const void* dP
   const int64_t rows = B * N;
   const int nblk = th_bwd_blocks(rows);
   float* part = reinterpret_cast<float*>(workspace);
-  const size_t va = dtype == VITMI_BF16 ? 8 : 16;
-  const bool vec = ld % 4 == 0 && ld >= (Nk + 3) / 4 * 4 && is_aligned(S, va) && is_aligned(P, va) && is_aligned(dPm, va) && is_aligned(dS, va);
+  if (th_long((int)H, (int)Nk)) {
+    const size_t lds = th_long_lds((int)H, (int)Nk, 2);
+#define TH_LBWD(T, HM)                                                                                                 \
+  do {                                                                                                                 \
+    if ((rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(th_long_softmax_bwd_kernel<T, HM>), (int)lds, "th_softmax_bwd"))) return rc; \
+    hipLaunchKernelGGL((th_long_softmax_bwd_kernel<T, HM>), dim3(nblk), dim3(256), lds, stream, (const T*)S, (const T*)P, (const T*)dPm, Wl, Ww, (T*)dS, part, rows, (int)H, (int)N, (int)Nk, (int)ld); \
+  } while (0)
+    if (dtype == VITMI_BF16) { if (H > 8) TH_LBWD(bf16, 16); else TH_LBWD(bf16, 8); }
+    else if (dtype == VITMI_F32) { if (H > 8) TH_LBWD(float, 16); else TH_LBWD(float, 8); }
+    else return vitmi_fail(VITMI_E_DTYPE, "th_softmax_bwd: bad dtype");
+#undef TH_LBWD
+    rc = vitmi_check_launch("th_long_softmax_bwd_kernel");
+  } else {
+    const size_t va = dtype == VITMI_BF16 ? 8 : 16;
+    const bool vec = ld % 4 == 0 && ld >= (Nk + 3) / 4 * 4 && is_aligned(S, va) && is_aligned(P, va) && is_aligned(dPm, va) && is_aligned(dS, va);
 #define TH_BWD(T, V, MFV) hipLaunchKernelGGL((th_softmax_bwd_kernel<T, V, MFV>), dim3(nblk), dim3(256), 0, stream, (const T*)S, (const T*)P, (const T*)dPm, Wl, Ww, (T*)dS, part, rows, (int)H, (int)N, (int)Nk, (int)ld)
-  const bool mf = g_th_mfma != 0 && vec && dtype == VITMI_BF16 && ld % 8 == 0 && is_aligned(S, 16) && is_aligned(P, 16) && is_aligned(dPm, 16);
-  if (dtype == VITMI_BF16) { if (mf) TH_BWD(bf16, true, true); else if (vec) TH_BWD(bf16, true, false); else TH_BWD(bf16, false, false); }
-  else if (dtype == VITMI_F32) { if (vec) TH_BWD(float, true, false); else TH_BWD(float, false, false); }
-  else return vitmi_fail(VITMI_E_DTYPE, "th_softmax_bwd: bad dtype");
+    const bool mf = g_th_mfma != 0 && vec && dtype == VITMI_BF16 && ld % 8 == 0 && is_aligned(S, 16) && is_aligned(P, 16) && is_aligned(dPm, 16);
+    if (dtype == VITMI_BF16) { if (mf) TH_BWD(bf16, true, true); else if (vec) TH_BWD(bf16, true, false); else TH_BWD(bf16, false, false); }
+    else if (dtype == VITMI_F32) { if (vec) TH_BWD(float, true, false); else TH_BWD(float, false, false); }
+    else return vitmi_fail(VITMI_E_DTYPE, "th_softmax_bwd: bad dtype");
 #undef TH_BWD
-  rc = vitmi_check_launch("th_softmax_bwd_kernel");
+    rc = vitmi_check_launch("th_softmax_bwd_kernel");
+  }
   if (rc) return rc;
   const int64_t stride = 2 * H * H + 2 * H;
   const int nrows = nblk;                          // one partial row per workgroup
@@ -828,17 +1132,22 @@ extern "C" int vitmi_class_attn_fwd(const void* q, const void* k, const void* v,
                                     void* out, float* p_save, int dtype, int64_t B, int64_t H, int64_t N,
                                     int64_t hd, float scale, void* stream_) {
   VITMI_REQUIRE(q && k && v && out && p_save && B > 0 && H > 0 && N > 0, VITMI_E_BADARG, "class_attn_fwd: bad argument");
-  VITMI_REQUIRE(hd >= 1 && hd <= 64 && N <= 64 * TH_MAXC, VITMI_E_SHAPE, "class_attn_fwd: hd <= 64 and N <= %d required", 64 * TH_MAXC);
+  VITMI_REQUIRE(hd >= 1 && hd <= 64 && N <= CA_MAXN_LONG, VITMI_E_SHAPE, "class_attn_fwd: hd <= 64 and N <= %d required", CA_MAXN_LONG);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const int64_t BH = B * H;
   dim3 grid((unsigned)((BH + 3) / 4));
-  if (dtype == VITMI_BF16 && hd % 8 == 0 && kv_token_stride % 8 == 0 && is_aligned(q, 16) && is_aligned(k, 16) && is_aligned(v, 16) && is_aligned(out, 16))
-    hipLaunchKernelGGL(class_attn_fwd_vec_kernel, grid, dim3(256), 0, stream, (const bf16*)q, (const bf16*)k, (const bf16*)v, kv_token_stride, (bf16*)out, p_save, BH, (int)H, (int)N, (int)hd, scale);
-  else if (dtype == VITMI_BF16)
-    hipLaunchKernelGGL((class_attn_fwd_kernel<bf16>), grid, dim3(256), 0, stream, (const bf16*)q, (const bf16*)k, (const bf16*)v, kv_token_stride, (bf16*)out, p_save, BH, (int)H, (int)N, (int)hd, scale);
-  else if (dtype == VITMI_F32)
-    hipLaunchKernelGGL((class_attn_fwd_kernel<float>), grid, dim3(256), 0, stream, (const float*)q, (const float*)k, (const float*)v, kv_token_stride, (float*)out, p_save, BH, (int)H, (int)N, (int)hd, scale);
-  else return vitmi_fail(VITMI_E_DTYPE, "class_attn_fwd: bad dtype");
+  const bool lng = N > 64 * TH_MAXC;                // the long forms only for rows the short ones refuse
+#define CA_FWD_VEC(ST) hipLaunchKernelGGL((class_attn_fwd_vec_kernel<ST>), grid, dim3(256), 0, stream, (const bf16*)q, (const bf16*)k, (const bf16*)v, kv_token_stride, (bf16*)out, p_save, BH, (int)H, (int)N, (int)hd, scale)
+#define CA_FWD(T, MC) hipLaunchKernelGGL((class_attn_fwd_kernel<T, MC>), grid, dim3(256), 0, stream, (const T*)q, (const T*)k, (const T*)v, kv_token_stride, (T*)out, p_save, BH, (int)H, (int)N, (int)hd, scale)
+  if (dtype == VITMI_BF16 && hd % 8 == 0 && kv_token_stride % 8 == 0 && is_aligned(q, 16) && is_aligned(k, 16) && is_aligned(v, 16) && is_aligned(out, 16)) {
+    if (lng) CA_FWD_VEC(CA_LONG_STEPS); else CA_FWD_VEC(CA_STEPS);
+  } else if (dtype == VITMI_BF16) {
+    if (lng) CA_FWD(bf16, CA_LONG_MAXC); else CA_FWD(bf16, TH_MAXC);
+  } else if (dtype == VITMI_F32) {
+    if (lng) CA_FWD(float, CA_LONG_MAXC); else CA_FWD(float, TH_MAXC);
+  } else return vitmi_fail(VITMI_E_DTYPE, "class_attn_fwd: bad dtype");
+#undef CA_FWD_VEC
+#undef CA_FWD
   return vitmi_check_launch("class_attn_fwd_kernel");
 }
 
@@ -847,18 +1156,25 @@ extern "C" int vitmi_class_attn_bwd(const void* q, const void* k, const void* v,
                                     int64_t dkv_token_stride, int dtype, int64_t B, int64_t H, int64_t N,
                                     int64_t hd, float scale, void* stream_) {
   VITMI_REQUIRE(q && k && v && dout && p_save && dq && dk && dv && B > 0 && H > 0 && N > 0, VITMI_E_BADARG, "class_attn_bwd: bad argument");
-  VITMI_REQUIRE(hd >= 1 && hd <= 64 && N <= 64 * TH_MAXC, VITMI_E_SHAPE, "class_attn_bwd: hd <= 64 and N <= %d required", 64 * TH_MAXC);
+  VITMI_REQUIRE(hd >= 1 && hd <= 64 && N <= CA_MAXN_LONG, VITMI_E_SHAPE, "class_attn_bwd: hd <= 64 and N <= %d required", CA_MAXN_LONG);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const int64_t BH = B * H;
   dim3 grid((unsigned)((BH + 3) / 4));
+  const bool lng = N > 64 * TH_MAXC;
+#define CA_BWD_VEC(ST) hipLaunchKernelGGL((class_attn_bwd_vec_kernel<ST>), grid, dim3(256), 0, stream, (const bf16*)q, (const bf16*)k, (const bf16*)v, kv_token_stride, (const bf16*)dout, p_save, (bf16*)dq, (bf16*)dk, (bf16*)dv, dkv_token_stride, BH, (int)H, (int)N, (int)hd, scale)
+#define CA_BWD_LONG(T) hipLaunchKernelGGL((class_attn_bwd_long_kernel<T>), grid, dim3(256), 0, stream, (const T*)q, (const T*)k, (const T*)v, kv_token_stride, (const T*)dout, p_save, (T*)dq, (T*)dk, (T*)dv, dkv_token_stride, BH, (int)H, (int)N, (int)hd, scale)
+#define CA_BWD(T, MC) hipLaunchKernelGGL((class_attn_bwd_kernel<T, MC>), grid, dim3(256), 0, stream, (const T*)q, (const T*)k, (const T*)v, kv_token_stride, (const T*)dout, p_save, (T*)dq, (T*)dk, (T*)dv, dkv_token_stride, BH, (int)H, (int)N, (int)hd, scale)
   if (dtype == VITMI_BF16 && hd % 8 == 0 && kv_token_stride % 8 == 0 && dkv_token_stride % 8 == 0 && is_aligned(q, 16) && is_aligned(k, 16) &&
-      is_aligned(v, 16) && is_aligned(dout, 16) && is_aligned(dq, 16) && is_aligned(dk, 16) && is_aligned(dv, 16))
-    hipLaunchKernelGGL(class_attn_bwd_vec_kernel, grid, dim3(256), 0, stream, (const bf16*)q, (const bf16*)k, (const bf16*)v, kv_token_stride, (const bf16*)dout, p_save, (bf16*)dq, (bf16*)dk, (bf16*)dv, dkv_token_stride, BH, (int)H, (int)N, (int)hd, scale);
-  else if (dtype == VITMI_BF16)
-    hipLaunchKernelGGL((class_attn_bwd_kernel<bf16>), grid, dim3(256), 0, stream, (const bf16*)q, (const bf16*)k, (const bf16*)v, kv_token_stride, (const bf16*)dout, p_save, (bf16*)dq, (bf16*)dk, (bf16*)dv, dkv_token_stride, BH, (int)H, (int)N, (int)hd, scale);
-  else if (dtype == VITMI_F32)
-    hipLaunchKernelGGL((class_attn_bwd_kernel<float>), grid, dim3(256), 0, stream, (const float*)q, (const float*)k, (const float*)v, kv_token_stride, (const float*)dout, p_save, (float*)dq, (float*)dk, (float*)dv, dkv_token_stride, BH, (int)H, (int)N, (int)hd, scale);
-  else return vitmi_fail(VITMI_E_DTYPE, "class_attn_bwd: bad dtype");
+      is_aligned(v, 16) && is_aligned(dout, 16) && is_aligned(dq, 16) && is_aligned(dk, 16) && is_aligned(dv, 16)) {
+    if (lng) CA_BWD_VEC(CA_LONG_STEPS); else CA_BWD_VEC(CA_STEPS);
+  } else if (dtype == VITMI_BF16) {
+    if (lng) CA_BWD_LONG(bf16); else CA_BWD(bf16, TH_MAXC);
+  } else if (dtype == VITMI_F32) {
+    if (lng) CA_BWD_LONG(float); else CA_BWD(float, TH_MAXC);
+  } else return vitmi_fail(VITMI_E_DTYPE, "class_attn_bwd: bad dtype");
+#undef CA_BWD_VEC
+#undef CA_BWD
+#undef CA_BWD_LONG
   return vitmi_check_launch("class_attn_bwd_kernel");
 }
 

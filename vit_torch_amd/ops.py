@@ -516,6 +516,85 @@ def th_softmax_bwd(S, P, dPm, Wl, Ww, dS, dWl, dbl, dWw, dbw, B, H, N, Nk, ld):
           "vitmi_th_softmax_bwd")
 
 
+TH_LONG_MAXH, TH_LONG_MAXN = 16, 1024      # th_softmax_fwd / _bwd limits (cait_ops.hip TH_LONG_MAXH / TH_LONG_MAXC)
+
+
+def th_scores_softmax(qkv, Wl, bl, Ww, bw, B, H, N, hd, scale, NS):
+    """The first two of the three calls: S = scale q k^T into [B,H,N,NS] score rows, then the talking-heads softmax.
+    Returns (S, P, Pm)."""
+    D, D3 = H * hd, 3 * H * hd
+    S = torch.empty((B, H, N, NS), dtype=qkv.dtype, device=qkv.device)
+    gemm_batched(qkv, qkv, S, M=N, N=N, K=hd, lda=D3, ldb=D3, ldc=NS, a_kmajor=True, b_kmajor=True,
+                 batch=B * H, batch_inner=H, a_bs=(N * D3, hd), b_bs=(N * D3, hd),
+                 c_bs=(H * N * NS, N * NS), b_off=D, alpha=scale)
+    P, Pm = torch.empty_like(S), torch.empty_like(S)
+    th_softmax_fwd(S, Wl, bl, Ww, bw, P, Pm, B, H, N, N, NS)
+    return S, P, Pm
+
+
+def th_three_call_fwd(qkv, Wl, bl, Ww, bw, O, B, H, N, hd, scale, NS):
+    """Talking-heads attention in three calls: th_scores_softmax, then O [B*N, H*hd] = P' v.  Returns (S, P, Pm) for
+    th_three_call_bwd."""
+    D, D3 = H * hd, 3 * H * hd
+    S, P, Pm = th_scores_softmax(qkv, Wl, bl, Ww, bw, B, H, N, hd, scale, NS)
+    gemm_batched(Pm, qkv, O, M=N, N=hd, K=N, lda=NS, ldb=D3, ldc=D, a_kmajor=True, b_kmajor=False,
+                 batch=B * H, batch_inner=H, a_bs=(H * N * NS, N * NS), b_bs=(N * D3, hd),
+                 c_bs=(N * D, hd), b_off=2 * D)
+    return S, P, Pm
+
+
+def th_three_call_bwd(qkv, dO, S, P, Pm, Wl, Ww, dqkv, dWl, dbl, dWw, dbw, B, H, N, hd, scale, NS):
+    """Backward of th_three_call_fwd: dq, dk, dv into dqkv [B*N, 3*H*hd] and the four mixing-parameter gradients.
+    The transients dP' and dS are dropped as soon as their last product has been queued."""
+    D, D3 = H * hd, 3 * H * hd
+    dPm = torch.empty_like(S)
+    gemm_batched(dO, qkv, dPm, M=N, N=N, K=hd, lda=D, ldb=D3, ldc=NS, a_kmajor=True, b_kmajor=True,
+                 batch=B * H, batch_inner=H, a_bs=(N * D, hd), b_bs=(N * D3, hd),
+                 c_bs=(H * N * NS, N * NS), b_off=2 * D)
+    dS = torch.empty_like(S)
+    th_softmax_bwd(S, P, dPm, Wl, Ww, dS, dWl, dbl, dWw, dbw, B, H, N, N, NS)
+    del dPm
+    gemm_batched(dS, qkv, dqkv, M=N, N=hd, K=N, lda=NS, ldb=D3, ldc=D3, a_kmajor=True, b_kmajor=False,
+                 batch=B * H, batch_inner=H, a_bs=(H * N * NS, N * NS), b_bs=(N * D3, hd),
+                 c_bs=(N * D3, hd), b_off=D, alpha=scale)                                  # dQ = scale dS K
+    gemm_batched(Pm, dO, dqkv, M=N, N=hd, K=N, lda=NS, ldb=D, ldc=D3, a_kmajor=False, b_kmajor=False,
+                 batch=B * H, batch_inner=H, a_bs=(H * N * NS, N * NS), b_bs=(N * D, hd),
+                 c_bs=(N * D3, hd), c_off=2 * D)                                           # dV = P'^T dO
+    gemm_batched(dS, qkv, dqkv, M=N, N=hd, K=N, lda=NS, ldb=D3, ldc=D3, a_kmajor=False, b_kmajor=False,
+                 batch=B * H, batch_inner=H, a_bs=(H * N * NS, N * NS), b_bs=(N * D3, hd),
+                 c_bs=(N * D3, hd), c_off=D, alpha=scale)                                  # dK = scale dS^T Q
+
+
+def th_long_supported(t, H, N, hd) -> bool:
+    """Host-only query: does the long-sequence talking-heads op (th_long_fwd / _bwd) take this shape / dtype?  bf16 only:
+    the parity modes keep their scores (th_three_call_*); the limits are those of th_softmax_fwd / _bwd."""
+    return t == torch.bfloat16 and 1 <= H <= TH_LONG_MAXH and 1 <= N <= TH_LONG_MAXN and hd >= 1
+
+
+def _th_long_check(qkv, B, H, N, hd):
+    if not th_long_supported(qkv.dtype, H, N, hd):
+        raise _lib.VitmiError(f"th_long: bf16 with H <= {TH_LONG_MAXH} heads and N <= {TH_LONG_MAXN} tokens required "
+                         f"(got {qkv.dtype}, H = {H}, N = {N}, hd = {hd})")
+    assert qkv.is_contiguous() and qkv.numel() == B * N * 3 * H * hd
+
+
+def th_long_fwd(qkv, Wl, bl, Ww, bw, O, B, H, N, hd, scale):
+    """Talking-heads attention that keeps nothing quadratic: O [B*N, H*hd] as th_three_call_fwd computes it, with the
+    score tensors dropped on return.  th_long_bwd recomputes them from qkv, one layer at a time."""
+    _th_long_check(qkv, B, H, N, hd)
+    th_three_call_fwd(qkv, Wl, bl, Ww, bw, O, B, H, N, hd, scale, (N + 7) // 8 * 8)
+    return O
+
+
+def th_long_bwd(qkv, dO, Wl, bl, Ww, bw, dqkv, dWl, dbl, dWw, dbw, B, H, N, hd, scale):
+    """Backward of th_long_fwd: recomputes S, P and P' (not O) and runs the three-call backward.  Peak transient: five
+    [B, H, N, ru8(N)] bf16 tensors (S, P, P', dP', dS) while the softmax backward runs, all freed before it returns."""
+    _th_long_check(qkv, B, H, N, hd)
+    NS = (N + 7) // 8 * 8
+    S, P, Pm = th_scores_softmax(qkv, Wl, bl, Ww, bw, B, H, N, hd, scale, NS)
+    th_three_call_bwd(qkv, dO, S, P, Pm, Wl, Ww, dqkv, dWl, dbl, dWw, dbw, B, H, N, hd, scale, NS)
+
+
 def th_attn_supported(t, H, N, hd) -> bool:
     """Host-only query: do the fused talking-heads kernels take this shape / dtype?"""
     code = (BF16 if t == torch.bfloat16 else F32 if t == torch.float32 else -1) if isinstance(t, torch.dtype) else dtype_code(t)
