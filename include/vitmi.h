@@ -421,6 +421,26 @@ int vitmi_ingest_patchify(const void* src_u8_nhwc, void* out, int out_dtype, int
                           int64_t B, int64_t H, int64_t W, int64_t C, int64_t S, int64_t pad, int64_t fill,
                           int64_t p, int cls_rows, void* stream);
 
+/* vitmi_image_ingest with the reference's resize in front (utils_datasets.py:553-582 when the stored size differs from
+ * S): Resize(BICUBIC) -> RandomCrop(S, padding, fill) -> RandomHorizontalFlip -> ToTensor -> Normalize, uint8 NHWC
+ * [B,H,W,C] -> fp32 NCHW [B,C,S,S].  The resize is Pillow's 8-bit ImagingResample, bit-exact: ytab / xtab are its
+ * fixed-point coefficient tables (int32 [2 + taps, Hr] / [2 + taps, Wr] = start, count, weights tap by tap; 22
+ * fractional bits; built on the host by vit_torch_amd/resize.py), the horizontal pass runs first and rounds to uint8.
+ * off_y/off_x/flip/mean/std/pad/fill as vitmi_image_ingest, over the resized Hr x Wr image.  taps <= 32, C <= 4.
+ * Additive to ABI 109. */
+int vitmi_resize_ingest(const void* src_u8_nhwc, float* dst_nchw, const int32_t* ytab, int64_t ytaps, int64_t Hr,
+                        const int32_t* xtab, int64_t xtaps, int64_t Wr, const int32_t* off_y, const int32_t* off_x,
+                        const uint8_t* flip, const float* mean, const float* std, int64_t B, int64_t H, int64_t W,
+                        int64_t C, int64_t S, int64_t pad, int64_t fill, void* stream);
+
+/* vitmi_resize_ingest written straight into patch rows, as vitmi_ingest_patchify: bit-identical to
+ * vitmi_resize_ingest followed by vitmi_patchify.  p % 4 == 0, S % p == 0, p <= 64.  Additive to ABI 109. */
+int vitmi_resize_ingest_patchify(const void* src_u8_nhwc, void* out, int out_dtype, int64_t out_ld, const int32_t* ytab,
+                                 int64_t ytaps, int64_t Hr, const int32_t* xtab, int64_t xtaps, int64_t Wr,
+                                 const int32_t* off_y, const int32_t* off_x, const uint8_t* flip, const float* mean,
+                                 const float* std, int64_t B, int64_t H, int64_t W, int64_t C, int64_t S, int64_t pad,
+                                 int64_t fill, int64_t p, int cls_rows, void* stream);
+
 /* optim.Adam / optim.AdamW step (utils_network.py:121,124; torch defaults betas (0.9, 0.999),
  * eps 1e-8, AdamW weight_decay 1e-2) over a flat buffer.  state[0] (device, fp32) is the step
  * count: it is advanced by this call BEFORE the update, so a captured HIP graph replays the

@@ -32,6 +32,7 @@ SOURCES = [
     "elementwise.hip",
     "split3.hip",
     "ingest.hip",
+    "resize.hip",
     "posembed.hip",
     "optim.hip",
     "attention.hip",

@@ -463,6 +463,44 @@ def ingest_patchify(src, out, off_y, off_x, flip, mean, std, S, pad, p, cls_rows
     return out
 
 
+def _resize_tables(ytab, xtab):
+    for t in (ytab, xtab):
+        assert t.is_cuda and t.dtype == torch.int32 and t.dim() == 2 and t.shape[0] >= 3 and t.is_contiguous()
+    return ytab.data_ptr(), ytab.shape[0] - 2, ytab.shape[1], xtab.data_ptr(), xtab.shape[0] - 2, xtab.shape[1]
+
+
+def resize_ingest(src, dst, ytab, xtab, off_y, off_x, flip, mean, std, pad, fill=128):
+    """src uint8 [B,H,W,C] (NHWC) -> Pillow bicubic to ytab.shape[1] x xtab.shape[1] -> crop/flip/normalize -> dst fp32
+    [B,C,S,S]; tables from vit_torch_amd.resize.table.  See vitmi_resize_ingest."""
+    _need_cuda(src, dst)
+    assert src.dtype == torch.uint8 and src.is_contiguous() and dst.dtype == torch.float32 and dst.is_contiguous()
+    B, H, W, C = src.shape
+    assert dst.shape[0] == B and dst.shape[1] == C and dst.shape[2] == dst.shape[3]
+    for t, dt in ((off_y, torch.int32), (off_x, torch.int32), (flip, torch.uint8), (mean, torch.float32), (std, torch.float32)):
+        assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous())
+    check(load().vitmi_resize_ingest(src.data_ptr(), dst.data_ptr(), *_resize_tables(ytab, xtab), _ptr(off_y), _ptr(off_x),
+                                     _ptr(flip), _ptr(mean), _ptr(std), B, H, W, C, dst.shape[2], int(pad), int(fill),
+                                     _stream()), "vitmi_resize_ingest")
+    return dst
+
+
+def resize_ingest_patchify(src, out, ytab, xtab, off_y, off_x, flip, mean, std, S, pad, p, cls_rows, fill=128):
+    """resize_ingest written straight into patch rows [B*(cls_rows + (S/p)^2), ld >= C*p*p]; see
+    vitmi_resize_ingest_patchify."""
+    _need_cuda(src, out)
+    assert src.dtype == torch.uint8 and src.is_contiguous() and out.dim() == 2 and out.is_contiguous()
+    B, H, W, C = src.shape
+    g = S // p
+    assert out.shape[0] == B * (cls_rows + g * g) and out.shape[1] >= C * p * p
+    for t, dt in ((off_y, torch.int32), (off_x, torch.int32), (flip, torch.uint8), (mean, torch.float32), (std, torch.float32)):
+        assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous())
+    check(load().vitmi_resize_ingest_patchify(src.data_ptr(), out.data_ptr(), dtype_code(out), out.shape[1],
+                                              *_resize_tables(ytab, xtab), _ptr(off_y), _ptr(off_x), _ptr(flip), _ptr(mean),
+                                              _ptr(std), B, H, W, C, int(S), int(pad), int(fill), int(p), int(cls_rows),
+                                              _stream()), "vitmi_resize_ingest_patchify")
+    return out
+
+
 def adam(p, g, m, v, shadow, state, lr, beta1, beta2, eps, weight_decay, decoupled, grad_scale=1.0):
     _need_cuda(p, g, m, v, state)
     assert p.dtype == g.dtype == m.dtype == v.dtype == state.dtype == torch.float32
