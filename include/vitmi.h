@@ -224,6 +224,12 @@ int vitmi_fold_many(const vitmi_fold_desc* descs, int n, void* stream);
 int vitmi_attn_fwd(const void* qkv, void* out, float* lse, int dtype,
                    int64_t B, int64_t N, int64_t H, int64_t hd, float scale,
                    void* stream);
+/* The attention probabilities themselves, for DINO's get_last_selfattention: P[b,h,i,j] = softmax_j((q_i . k_j) * scale),
+ * fp32, contiguous [B, H, N, N] (4-byte aligned), from the same qkv [B, N, 3, H, hd] as vitmi_attn_fwd (bf16, or fp32 for the
+ * fp32 and bf16x3 modes; 16-byte aligned).  hd in {32, 64}, any N >= 1; other arguments fail before any launch.  Forward
+ * only.  Additive to ABI 109. */
+int vitmi_attn_probs(const void* qkv, float* P, int dtype, int64_t B, int64_t N, int64_t H, int64_t hd, float scale,
+                     void* stream);
 size_t vitmi_attn_bwd_workspace(int64_t B, int64_t N, int64_t H);
 /* dbias_part (optional, bf16 kernels only): fp32 [vitmi_attn_bwd_dbias_rows(B, N)][3*H*hd];
  * each row holds the column sums of the dqkv rows one workgroup produced, so their sum

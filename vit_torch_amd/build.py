@@ -37,6 +37,7 @@ SOURCES = [
     "optim.hip",
     "attention.hip",
     "attention_f32.hip",
+    "attn_probs.hip",
     "cait_ops.hip",
     "cait_fused.hip",
     "swin_ops.hip",

@@ -329,6 +329,23 @@ def attn_fwd(qkv, out, lse, B, N, H, hd, scale):
     return out
 
 
+def attn_probs(qkv, P, B, N, H, hd, scale):
+    """P [B, H, N, N] fp32 = softmax((q k^T) * scale) of qkv [B*N, 3*H*hd] (bf16 or fp32, as attn_fwd reads it):
+    the attention probabilities materialised (vitmi_attn_probs; DINO's get_last_selfattention).  Forward only."""
+    _need_cuda(qkv, P)
+    if qkv.dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.VitmiError(f"attn_probs: qkv must be bf16 or fp32, got {qkv.dtype}")
+    if P.dtype != torch.float32 or not P.is_contiguous() or P.numel() != B * H * N * N:
+        raise _lib.VitmiError(f"attn_probs: P must be a contiguous fp32 [B, H, N, N] = [{B}, {H}, {N}, {N}] tensor "
+                              f"(got {P.dtype}, {tuple(P.shape)})")
+    if not qkv.is_contiguous() or qkv.numel() != B * N * 3 * H * hd:
+        raise _lib.VitmiError(f"attn_probs: qkv must be a contiguous [B*N, 3*H*hd] = [{B * N}, {3 * H * hd}] tensor "
+                              f"(got {tuple(qkv.shape)})")
+    check(load().vitmi_attn_probs(qkv.data_ptr(), P.data_ptr(), dtype_code(qkv), B, N, H, hd, float(scale), _stream()),
+          "vitmi_attn_probs")
+    return P
+
+
 def attn_bwd_dbias_rows(B, N) -> int:
     return int(load().vitmi_attn_bwd_dbias_rows(B, N))
 

@@ -9,6 +9,9 @@ Differences, on purpose:
   * the dino branch applies the installed classifier (`apply_head=True`);
     upstream DINO's forward ignores `.head` ([recall]) — pass
     `apply_head=False` to get the raw upstream behaviour.
+  * the dino branch's model also has upstream's `get_last_selfattention(x)` and
+    `get_intermediate_layers(x, n=1)`, forward only (under `torch.no_grad()` or
+    with frozen parameters; vit.py).
 """
 from __future__ import annotations
 

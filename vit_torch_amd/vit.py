@@ -119,6 +119,31 @@ class VisionTransformer(EngineModel, nn.Module):
     def _new_engine(self) -> "VitEngine":
         return VitEngine(self)
 
+    # upstream DINO's two other public methods (facebookresearch/dino vision_transformer.py).  Forward only: they refuse
+    # to run where autograd would want a graph (call them under torch.no_grad() or with the backbone frozen); there is no
+    # backward through their outputs.  Both run every block in full, also with cls_only_last_block (and so also at
+    # N > 256 tokens, which that option's forward refuses).
+    def _introspection_engine(self, x, what):
+        if not x.is_cuda:
+            raise VitmiError("vit_torch_amd models run on an MI355X (HIP) device; got a CPU tensor "
+                             "and there is no CPU fallback")
+        eng = self.engine()
+        if torch.is_grad_enabled() and any(p.requires_grad for p in eng.pack.params):
+            raise VitmiError(f"{what} is forward-only (no backward through it): call it under torch.no_grad() or "
+                             "freeze the backbone (requires_grad_(False))")
+        return eng
+
+    def get_last_selfattention(self, x):
+        """The last block's attention probabilities softmax((q k^T) * scale), fp32 [B, num_heads, N, N], N = 1 + patches
+        (upstream: DINO's attention-map visualisation).  Accepts what forward accepts.  Forward only."""
+        return self._introspection_engine(x, "get_last_selfattention").last_selfattention(x)
+
+    def get_intermediate_layers(self, x, n=1):
+        """[self.norm(x) after each of the last n blocks], oldest first, each a fresh fp32 [B, N, embed_dim] over all
+        tokens (upstream: DINO's linear evaluation and dense features).  n = 0 gives [], n >= depth every block.
+        Accepts what forward accepts.  Forward only."""
+        return self._introspection_engine(x, "get_intermediate_layers").intermediate_layers(x, n)
+
 
 # ------------------------------------------------------------------ engine --
 class VitEngine(Engine):
@@ -158,34 +183,34 @@ class VitEngine(Engine):
         return ops.pos_resample(pos.reshape(-1, pos.shape[-1]), tabs.fwd), tabs
 
     # -- forward -------------------------------------------------------------
-    def forward(self, x, save: bool):
-        m, T, R = self.model, self.T, self.R
-        dev = x.device
-        pre = x if isinstance(x, PatchRows) else None          # device input pipeline: rows already gathered
-        if pre is None:
-            x = x.float() if x.dtype != torch.float32 else x
-            B, Cin, Himg, Wimg = x.shape
+    def _shape(self, x):
+        """Host-only: (B, N, M, D, H, hd, Kp, gh, gw) of an NCHW image tensor or PatchRows input."""
+        m = self.model
+        if isinstance(x, PatchRows):
+            B, Cin, Himg, Wimg = x.B, x.C, x.H, x.W
         else:
-            B, Cin, Himg, Wimg = pre.B, pre.C, pre.H, pre.W
+            B, Cin, Himg, Wimg = x.shape
         p = m.patch_embed.patch_size
         conv = m.patch_embed.proj
         if Cin != conv.in_channels:
             raise VitmiError(f"input has {Cin} channels, patch_embed.proj expects {conv.in_channels}")
         gh, gw = Himg // p, Wimg // p
         N = 1 + gh * gw
-        M = B * N
         D = m.embed_dim
         H = m.blocks[0].attn.num_heads
-        hd = D // H
-        Kp = Cin * p * p
-        if self.cls_last and N > 256:
-            raise VitmiError(f"cls_only_last_block needs at most 256 tokens per image (the class-attention kernels' limit); this "
-                             f"input has {N}: build the model without the option")
+        return B, N, B * N, D, H, D // H, Cin * p * p, gh, gw
+
+    def _embed(self, x, shape, new):
+        """Patch rows, then X = patch_embed(x) + pos_embed with the CLS row in front: the residual stream [M, D] (dtype R)
+        that enters block 0.  Returns (X, patches, pos_tabs)."""
+        m, T = self.model, self.T
+        B, N, M, D, H, hd, Kp, gh, gw = shape
+        p = m.patch_embed.patch_size
+        conv = m.patch_embed.proj
+        pre = x if isinstance(x, PatchRows) else None          # device input pipeline: rows already gathered
+        if pre is None:
+            x = x.float() if x.dtype != torch.float32 else x
         self.pack.refresh_shadow()
-
-        def new(rows, cols, dt):
-            return self._alloc(rows, cols, dt, dev)
-
         if pre is None:
             patches = new(M, Kp, T)
             ops.patchify(x, patches, p, cls_rows=1)
@@ -195,40 +220,68 @@ class VitEngine(Engine):
                                  f"does not fit this model (p={p}, cls_rows=1, {T}, {(M, Kp)})")
             patches = pre.rows
         pos, pos_tabs = self._pos_for(gh, gw)
-        X = new(M, D, R)
+        X = new(M, D, self.R)
         self._gemm(patches, self._w(conv.weight).view(D, Kp), X, epilogue=EPI_PATCH_POS,
                    bias=self.pack.f32(conv.bias) if conv.bias is not None else None,
                    pos=pos, n_tok=N, cls=self.pack.f32(m.cls_token).view(-1))
+        return X, patches, pos_tabs
+
+    def _ln1_qkv(self, blk, X, M, D, new, dev):
+        """norm1 and the qkv Linear of a block: (ln1, mean1, rstd1, qkv [M, 3D] dtype T)."""
+        a = blk.attn
+        ln1 = new(M, D, self.T)
+        mean1 = torch.empty(M, dtype=torch.float32, device=dev)
+        rstd1 = torch.empty(M, dtype=torch.float32, device=dev)
+        ops.layernorm_fwd(X, self.pack.f32(blk.norm1.weight), self.pack.f32(blk.norm1.bias), ln1,
+                          mean1, rstd1, blk.norm1.eps, M=M, D=D)
+        qkv = new(M, 3 * D, self.T)
+        self._gemm(ln1, self._w(a.qkv.weight), qkv,
+                   bias=self.pack.f32(a.qkv.bias) if a.qkv.bias is not None else None)
+        return ln1, mean1, rstd1, qkv
+
+    def _block_fwd(self, blk, X, B, N, M, D, H, hd, save, new, dev):
+        """One full block: X2 = X + attn(norm1(X)), then + mlp(norm2(.)), into new buffers.  Returns (X2, what the
+        backward needs or None)."""
+        T, R = self.T, self.R
+        a, mlp = blk.attn, blk.mlp
+        ln1, mean1, rstd1, qkv = self._ln1_qkv(blk, X, M, D, new, dev)
+        O = new(M, D, T)
+        lse = torch.empty(B * H * N, dtype=torch.float32, device=dev)
+        ops.attn_fwd(qkv, O, lse, B, N, H, hd, a.scale)
+        X1 = new(M, D, R)
+        self._gemm(O, self._w(a.proj.weight), X1, epilogue=EPI_RESIDUAL,
+                   bias=self.pack.f32(a.proj.bias), R=X)
+        ln2 = new(M, D, T)
+        mean2 = torch.empty(M, dtype=torch.float32, device=dev)
+        rstd2 = torch.empty(M, dtype=torch.float32, device=dev)
+        ops.layernorm_fwd(X1, self.pack.f32(blk.norm2.weight), self.pack.f32(blk.norm2.bias), ln2,
+                          mean2, rstd2, blk.norm2.eps, M=M, D=D)
+        X2, pre, hid = mlp_forward(self, mlp, ln2, X1, save)
+        saved = (X, ln1, mean1, rstd1, qkv, O, lse, X1, ln2, mean2, rstd2, pre, hid) if save else None
+        return X2, saved
+
+    def forward(self, x, save: bool):
+        m = self.model
+        dev = x.device
+        shape = self._shape(x)
+        B, N, M, D, H, hd, Kp, gh, gw = shape
+        if self.cls_last and N > 256:
+            raise VitmiError(f"cls_only_last_block needs at most 256 tokens per image (the class-attention kernels' limit); this "
+                             f"input has {N}: build the model without the option")
+
+        def new(rows, cols, dt):
+            return self._alloc(rows, cols, dt, dev)
+
+        X, patches, pos_tabs = self._embed(x, shape, new)
         blocks = []
         last_cls = None
         for bi_, blk in enumerate(m.blocks):
             if self.cls_last and bi_ == len(m.blocks) - 1:
                 X, last_cls = self._last_block_cls_fwd(blk, X, B, N, M, D, H, hd, save, new, dev)
                 break
-            a, mlp = blk.attn, blk.mlp
-            ln1 = new(M, D, T)
-            mean1 = torch.empty(M, dtype=torch.float32, device=dev)
-            rstd1 = torch.empty(M, dtype=torch.float32, device=dev)
-            ops.layernorm_fwd(X, self.pack.f32(blk.norm1.weight), self.pack.f32(blk.norm1.bias), ln1,
-                              mean1, rstd1, blk.norm1.eps, M=M, D=D)
-            qkv = new(M, 3 * D, T)
-            self._gemm(ln1, self._w(a.qkv.weight), qkv,
-                       bias=self.pack.f32(a.qkv.bias) if a.qkv.bias is not None else None)
-            O = new(M, D, T)
-            lse = torch.empty(B * H * N, dtype=torch.float32, device=dev)
-            ops.attn_fwd(qkv, O, lse, B, N, H, hd, a.scale)
-            X1 = new(M, D, R)
-            self._gemm(O, self._w(a.proj.weight), X1, epilogue=EPI_RESIDUAL,
-                       bias=self.pack.f32(a.proj.bias), R=X)
-            ln2 = new(M, D, T)
-            mean2 = torch.empty(M, dtype=torch.float32, device=dev)
-            rstd2 = torch.empty(M, dtype=torch.float32, device=dev)
-            ops.layernorm_fwd(X1, self.pack.f32(blk.norm2.weight), self.pack.f32(blk.norm2.bias), ln2,
-                              mean2, rstd2, blk.norm2.eps, M=M, D=D)
-            X2, pre, hid = mlp_forward(self, mlp, ln2, X1, save)
+            X, sv = self._block_fwd(blk, X, B, N, M, D, H, hd, save, new, dev)
             if save:
-                blocks.append((X, ln1, mean1, rstd1, qkv, O, lse, X1, ln2, mean2, rstd2, pre, hid))
-            X = X2
+                blocks.append(sv)
         feat = torch.empty((B, D), dtype=torch.float32, device=dev)
         meanf = torch.empty(B, dtype=torch.float32, device=dev)
         rstdf = torch.empty(B, dtype=torch.float32, device=dev)
@@ -241,6 +294,52 @@ class VitEngine(Engine):
                               Xf=X, meanf=meanf, rstdf=rstdf, head=head_saved,
                               pos_tabs=pos_tabs, last_cls=last_cls)
         return out
+
+    # -- upstream DINO's introspection methods (forward only, every block computed in full) -----------------------
+    def intermediate_layers(self, x, n: int):
+        """[norm(x) after block i for the last n blocks], oldest first, each a fresh fp32 [B, N, D] tensor."""
+        m = self.model
+        L = len(m.blocks)
+        n = max(0, min(int(n), L))
+        if n == 0:
+            return []
+        dev = x.device
+        shape = self._shape(x)
+        B, N, M, D, H, hd = shape[:6]
+
+        def new(rows, cols, dt):
+            return self._alloc(rows, cols, dt, dev)
+
+        X, _, _ = self._embed(x, shape, new)
+        outs = []
+        for bi_, blk in enumerate(m.blocks):
+            X, _ = self._block_fwd(blk, X, B, N, M, D, H, hd, False, new, dev)
+            if L - bi_ <= n:
+                y = torch.empty((M, D), dtype=torch.float32, device=dev)
+                ops.layernorm_fwd(X, self.pack.f32(m.norm.weight), self.pack.f32(m.norm.bias), y,
+                                  torch.empty(M, dtype=torch.float32, device=dev),
+                                  torch.empty(M, dtype=torch.float32, device=dev), m.norm.eps, M=M, D=D)
+                outs.append(y.view(B, N, D))
+        return outs
+
+    def last_selfattention(self, x):
+        """softmax((q k^T) * scale) of the last block, fp32 [B, H, N, N]: blocks 0 .. L-2 in full, then only the last
+        block's norm1, qkv Linear and the probabilities (vitmi_attn_probs)."""
+        m = self.model
+        dev = x.device
+        shape = self._shape(x)
+        B, N, M, D, H, hd = shape[:6]
+
+        def new(rows, cols, dt):
+            return self._alloc(rows, cols, dt, dev)
+
+        X, _, _ = self._embed(x, shape, new)
+        for blk in list(m.blocks)[:-1]:
+            X, _ = self._block_fwd(blk, X, B, N, M, D, H, hd, False, new, dev)
+        last = m.blocks[-1]
+        qkv = self._ln1_qkv(last, X, M, D, new, dev)[3]
+        P = torch.empty((B, H, N, N), dtype=torch.float32, device=dev)
+        return ops.attn_probs(qkv, P, B, N, H, hd, last.attn.scale)
 
     # -- the last block on the CLS row only (cls_only_last_block) ------------------
     def _last_block_cls_fwd(self, blk, X, B, N, M, D, H, hd, save, new, dev):
