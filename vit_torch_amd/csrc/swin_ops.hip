@@ -9,8 +9,9 @@
 //    scatter (:317-323), token mean (AdaptiveAvgPool1d, :584).
 // Two implementations: fp32 vector kernels (any hd <= 64, both dtypes: the parity mode) with
 // one workgroup per (window, head), and the bf16 MFMA kernels for hd = 32 (every Swin variant
-// at window 7) with one WAVE per (window, head) — "MFMA path" below.  Windows of 65..144 tokens
-// (window 12) have their own pair of each, further down.
+// at window 7) with one WAVE per (window, head) — "MFMA path" below.  The vector kernels serve every window
+// (one family, lanes own 1 or 3 keys); windows of 65..144 tokens (window 12) have MFMA kernels of their own,
+// further down.
 #include <atomic>
 #include "common.h"
 
@@ -30,25 +31,31 @@ __device__ __forceinline__ int64_t win_token(const WinGeom& g, int64_t bw, int i
   return b * (int64_t)g.Himg * g.Wimg + (int64_t)y * g.Wimg + x;
 }
 
+// The fp32 vector kernels, one family for every window: template constant C = 64-lane groups per score row, so
+// a lane owns the keys (or queries) lane + 64c, c < C: C = 1 serves N <= 64, C = 3 serves N <= 144.  Sums run
+// over c ascending, then j ascending inside a group.  LDS: [N][hd+1] fp32 images, 3 (forward) / 4 (backward) of
+// them (112 / 150 KB at N = 144, hd = 64).  (dQ alone is still a pair, see win_attn_bwd_dq_kernel.)
+
 // stage rows [N][hd] of one head (through the window map) into LDS, row stride hd+1
 template <typename T>
-__device__ __forceinline__ void stage_win(float* lds, const T* base, int64_t ts, const WinGeom& g,
-                                          int64_t bw, int N, int hd, int tid) {
-  for (int idx = tid; idx < 64 * hd; idx += 256) {
+__device__ __forceinline__ void stage_win(float* lds, const T* base, int64_t ts, const WinGeom& g, int64_t bw, int N,
+                                          int hd, int tid) {
+  for (int idx = tid; idx < N * hd; idx += 256) {
     const int r = idx / hd, d = idx % hd;
-    lds[r * (hd + 1) + d] = r < N ? to_f32(base[win_token(g, bw, r) * ts + d]) : 0.f;
+    lds[r * (hd + 1) + d] = to_f32(base[win_token(g, bw, r) * ts + d]);
   }
 }
 
-template <typename T>
+template <typename T, int C>
 __global__ __launch_bounds__(256) void win_attn_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ out,
                                                           float* __restrict__ lse, const float* __restrict__ bias,
                                                           const float* __restrict__ mask, WinGeom g, int H, int N,
                                                           int hd, float scale) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int hp = hd + 1;
   float* Qs = sm;
-  float* Ks = Qs + 64 * (hd + 1);
-  float* Vs = Ks + 64 * (hd + 1);
+  float* Ks = Qs + N * hp;
+  float* Vs = Ks + N * hp;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int64_t bw = blockIdx.x;
   const int h = blockIdx.y;
@@ -58,20 +65,36 @@ __global__ __launch_bounds__(256) void win_attn_fwd_kernel(const T* __restrict__
   stage_win(Vs, qkv + (2 * H + h) * hd, ts, g, bw, N, hd, tid);
   __syncthreads();
   const float* mrow = mask ? mask + (bw % g.nW) * (int64_t)N * N : nullptr;
+  const int dl = lane < hd ? lane : 0;
   for (int i = w; i < N; i += 4) {
-    float s = -INFINITY;
-    if (lane < N) {
-      s = 0.f;
-      for (int d = 0; d < hd; ++d) s = fmaf(Qs[i * (hd + 1) + d] * scale, Ks[lane * (hd + 1) + d], s);
-      s += bias[((int64_t)h * N + i) * N + lane];
-      if (mrow) s += mrow[i * N + lane];
+    float s[C], mx = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const int k = lane + 64 * c;
+      s[c] = -INFINITY;
+      if (k < N) {
+        float a = 0.f;
+        for (int d = 0; d < hd; ++d) a = fmaf(Qs[i * hp + d] * scale, Ks[k * hp + d], a);
+        a += bias[((int64_t)h * N + i) * N + k];
+        if (mrow) a += mrow[i * N + k];
+        s[c] = a;
+      }
+      mx = fmaxf(mx, s[c]);
     }
-    const float mx = wave_max(s);
-    const float p = expf(s - mx);
-    const float sum = wave_sum(p);
+    mx = wave_max(mx);
+    float p[C], sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      p[c] = lane + 64 * c < N ? expf(s[c] - mx) : 0.f;
+      sum += p[c];
+    }
+    sum = wave_sum(sum);
     float acc = 0.f;
-    const int dl = lane < hd ? lane : 0;
-    for (int j = 0; j < N; ++j) acc = fmaf(__shfl(p, j), Vs[j * (hd + 1) + dl], acc);
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const int jn = min(N - 64 * c, 64);
+      for (int j = 0; j < jn; ++j) acc = fmaf(__shfl(p[c], j), Vs[(64 * c + j) * hp + dl], acc);
+    }
     const int64_t tok = win_token(g, bw, i);
     if (lane < hd) out[tok * H * hd + h * hd + lane] = from_f32<T>(acc / sum);
     if (lane == 0) lse[(bw * H + h) * N + i] = mx + logf(sum);
@@ -536,7 +559,8 @@ __global__ __launch_bounds__(256) void win_attn_bwd_mfma_kernel(const bf16* __re
   }
 }
 
-// dQ + delta + dBias (per-window partial): wave per query row
+// dQ + delta + dBias (per-window partial), N <= 64: wave per query row, one key per lane.  Kept beside the walking
+// kernel below: as its one-group case that loop holds 47 VGPRs and spills 50 SGPRs where this holds 42 and none.
 template <typename T>
 __global__ __launch_bounds__(256) void win_attn_bwd_dq_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
                                                              const float* __restrict__ lse, const float* __restrict__ bias,
@@ -545,9 +569,9 @@ __global__ __launch_bounds__(256) void win_attn_bwd_dq_kernel(const T* __restric
                                                              WinGeom g, int H, int N, int hd, float scale) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* Qs = sm;
-  float* Ks = Qs + 64 * (hd + 1);
-  float* Vs = Ks + 64 * (hd + 1);
-  float* dOs = Vs + 64 * (hd + 1);
+  float* Ks = Qs + N * (hd + 1);
+  float* Vs = Ks + N * (hd + 1);
+  float* dOs = Vs + N * (hd + 1);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int64_t bw = blockIdx.x;
   const int h = blockIdx.y;
@@ -580,18 +604,90 @@ __global__ __launch_bounds__(256) void win_attn_bwd_dq_kernel(const T* __restric
   }
 }
 
-// dK, dV: wave per key row, lanes = queries
+// dQ, delta and d(bias): grid (R, H), workgroup (r, h) walks windows r, r + R, ... of head h and accumulates its
+// d(score) in partial row r of [R][H][N][N] (each element read and written by one thread only: deterministic).
+// 64 < N <= 144: three keys per lane.
 template <typename T>
+__global__ __launch_bounds__(256) void win_attn_bwd_dq_big_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
+                                                             const float* __restrict__ lse, const float* __restrict__ bias,
+                                                             const float* __restrict__ mask, T* __restrict__ dqkv,
+                                                             float* __restrict__ delta, float* __restrict__ dbias_part,
+                                                             WinGeom g, int H, int N, int hd, float scale, int64_t Bw) {
+  constexpr int C = 3;
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int hp = hd + 1;
+  float* Qs = sm;
+  float* Ks = Qs + N * hp;
+  float* Vs = Ks + N * hp;
+  float* dOs = Vs + N * hp;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int h = blockIdx.y;
+  const int64_t ts = (int64_t)3 * H * hd, os = (int64_t)H * hd;
+  const int dl = lane < hd ? lane : 0;
+  float* part = dbias_part + ((int64_t)blockIdx.x * H + h) * N * N;
+  for (int64_t bw = blockIdx.x; bw < Bw; bw += gridDim.x) {
+    const bool first = bw == (int64_t)blockIdx.x;
+    __syncthreads();                               // the previous window's LDS reads are done
+    stage_win(Qs, qkv + h * hd, ts, g, bw, N, hd, tid);
+    stage_win(Ks, qkv + (H + h) * hd, ts, g, bw, N, hd, tid);
+    stage_win(Vs, qkv + (2 * H + h) * hd, ts, g, bw, N, hd, tid);
+    stage_win(dOs, dout + h * hd, os, g, bw, N, hd, tid);
+    __syncthreads();
+    const float* mrow = mask ? mask + (bw % g.nW) * (int64_t)N * N : nullptr;
+    for (int i = w; i < N; i += 4) {
+      const float l = lse[(bw * H + h) * N + i];
+      float p[C], dp[C], pd = 0.f;
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const int k = lane + 64 * c;
+        p[c] = 0.f;
+        dp[c] = 0.f;
+        if (k < N) {
+          float s = 0.f, e = 0.f;
+          for (int d = 0; d < hd; ++d) {
+            s = fmaf(Qs[i * hp + d] * scale, Ks[k * hp + d], s);
+            e = fmaf(dOs[i * hp + d], Vs[k * hp + d], e);
+          }
+          s += bias[((int64_t)h * N + i) * N + k];
+          if (mrow) s += mrow[i * N + k];
+          p[c] = expf(s - l);
+          dp[c] = e;
+        }
+        pd = fmaf(p[c], dp[c], pd);
+      }
+      const float del = wave_sum(pd);
+      float ds[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const int k = lane + 64 * c;
+        ds[c] = p[c] * (dp[c] - del);
+        if (k < N) part[i * N + k] = first ? ds[c] : part[i * N + k] + ds[c];
+      }
+      if (lane == 0) delta[(bw * H + h) * N + i] = del;
+      float acc = 0.f;
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const int jn = min(N - 64 * c, 64);
+        for (int j = 0; j < jn; ++j) acc = fmaf(__shfl(ds[c], j), Ks[(64 * c + j) * hp + dl], acc);
+      }
+      if (lane < hd) dqkv[win_token(g, bw, i) * ts + h * hd + lane] = from_f32<T>(acc * scale);
+    }
+  }
+}
+
+// dK, dV: wave per key row, lanes = queries lane + 64c
+template <typename T, int C>
 __global__ __launch_bounds__(256) void win_attn_bwd_dkdv_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                const float* __restrict__ bias, const float* __restrict__ mask,
                                                                T* __restrict__ dqkv, WinGeom g, int H, int N, int hd,
                                                                float scale) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int hp = hd + 1;
   float* Qs = sm;
-  float* Ks = Qs + 64 * (hd + 1);
-  float* Vs = Ks + 64 * (hd + 1);
-  float* dOs = Vs + 64 * (hd + 1);
+  float* Ks = Qs + N * hp;
+  float* Vs = Ks + N * hp;
+  float* dOs = Vs + N * hp;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int64_t bw = blockIdx.x;
   const int h = blockIdx.y;
@@ -602,24 +698,34 @@ __global__ __launch_bounds__(256) void win_attn_bwd_dkdv_kernel(const T* __restr
   stage_win(dOs, dout + h * hd, os, g, bw, N, hd, tid);
   __syncthreads();
   const float* mrow = mask ? mask + (bw % g.nW) * (int64_t)N * N : nullptr;
+  const int dl = lane < hd ? lane : 0;
   for (int j = w; j < N; j += 4) {
-    float p = 0.f, ds = 0.f;
-    if (lane < N) {                                  // lane = query i
-      float s = 0.f, dp = 0.f;
-      for (int d = 0; d < hd; ++d) {
-        s = fmaf(Qs[lane * (hd + 1) + d] * scale, Ks[j * (hd + 1) + d], s);
-        dp = fmaf(dOs[lane * (hd + 1) + d], Vs[j * (hd + 1) + d], dp);
+    float p[C], ds[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const int i = lane + 64 * c;                 // query
+      p[c] = 0.f;
+      ds[c] = 0.f;
+      if (i < N) {
+        float s = 0.f, dp = 0.f;
+        for (int d = 0; d < hd; ++d) {
+          s = fmaf(Qs[i * hp + d] * scale, Ks[j * hp + d], s);
+          dp = fmaf(dOs[i * hp + d], Vs[j * hp + d], dp);
+        }
+        s += bias[((int64_t)h * N + i) * N + j];
+        if (mrow) s += mrow[i * N + j];
+        p[c] = expf(s - lse[(bw * H + h) * N + i]);
+        ds[c] = p[c] * (dp - delta[(bw * H + h) * N + i]);
       }
-      s += bias[((int64_t)h * N + lane) * N + j];
-      if (mrow) s += mrow[lane * N + j];
-      p = expf(s - lse[(bw * H + h) * N + lane]);
-      ds = p * (dp - delta[(bw * H + h) * N + lane]);
     }
     float ak = 0.f, av = 0.f;
-    const int dl = lane < hd ? lane : 0;
-    for (int i = 0; i < N; ++i) {
-      ak = fmaf(__shfl(ds, i), Qs[i * (hd + 1) + dl], ak);
-      av = fmaf(__shfl(p, i), dOs[i * (hd + 1) + dl], av);
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const int in = min(N - 64 * c, 64);
+      for (int i = 0; i < in; ++i) {
+        ak = fmaf(__shfl(ds[c], i), Qs[(64 * c + i) * hp + dl], ak);
+        av = fmaf(__shfl(p[c], i), dOs[(64 * c + i) * hp + dl], av);
+      }
     }
     if (lane < hd) {
       T* row = dqkv + win_token(g, bw, j) * ts + h * hd + lane;
@@ -637,32 +743,34 @@ __global__ void relpos_gather_kernel(const float* __restrict__ table, const int6
   const int h = t / NN, ij = t % NN;
   bias[t] = table[index[ij] * H + h];
 }
-// dtable[t][h] = sum_{ij: index[ij]==t} dbias[h][ij]: one workgroup per table row t.  Phase 1: the threads scan
-// the index ONCE and compact the matching positions (at most N of the N*N) into LDS in a FIXED slot order
-// ((iteration, wave) slots, ballot-ranked inside a slot); phase 2: one thread per head sums its <= N values in that
-// order (deterministic, no atomics).  (Round 2 scanned the whole index once per head and wave: 33 us per call.)
+// dtable[t][h] = sum_{ij: index[ij]==t} dbias[h][ij]: one workgroup per table row t.  Phase 1: the threads scan the
+// index ONCE and compact the matching positions (at most N <= 144 of the N*N for an index of models/swin.py:120-129)
+// into one LDS list in ascending position order, through a per-iteration prefix of the four waves' ballot counts;
+// phase 2: one thread per head sums its values in that order (deterministic, no atomics).
+constexpr int RP_LIST = 256;
 __global__ __launch_bounds__(256) void relpos_scatter_kernel(const float* __restrict__ dbias,
                                                             const int64_t* __restrict__ index,
                                                             float* __restrict__ dtable, int T, int H, int NN) {
-  __shared__ int list[64 * 64];        // NN <= 4096: 16 iterations x 4 waves slots of up to 64 hits
-  __shared__ int cnt[64];
+  __shared__ int list[RP_LIST];
+  __shared__ int cnt[4];
   const int t = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int iters = (NN + 255) / 256;
-  for (int it = 0; it < iters; ++it) {
-    const int ij = it * 256 + threadIdx.x;
+  int total = 0;
+  for (int base = 0; base < NN; base += 256) {
+    const int ij = base + threadIdx.x;
     const bool hit = ij < NN && index[ij] == t;
     const unsigned long long m = __ballot(hit);
-    const int slot = it * 4 + w;
-    if (hit) list[slot * 64 + __popcll(m & ((1ull << lane) - 1ull))] = ij;
-    if (lane == 0) cnt[slot] = __popcll(m);
+    if (lane == 0) cnt[w] = __popcll(m);
+    __syncthreads();
+    int pos = total + __popcll(m & ((1ull << lane) - 1ull));
+    for (int v = 0; v < w; ++v) pos += cnt[v];
+    if (hit && pos < RP_LIST) list[pos] = ij;
+    total += cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    __syncthreads();
   }
-  __syncthreads();
+  const int c = min(total, RP_LIST);
   for (int h = threadIdx.x; h < H; h += 256) {
     float s = 0.f;
-    for (int slot = 0; slot < iters * 4; ++slot) {
-      const int c = cnt[slot];
-      for (int e = 0; e < c; ++e) s += dbias[(int64_t)h * NN + list[slot * 64 + e]];
-    }
+    for (int e = 0; e < c; ++e) s += dbias[(int64_t)h * NN + list[e]];
     dtable[(int64_t)t * H + h] = s;
   }
 }
@@ -712,212 +820,11 @@ __global__ void token_mean_bwd_kernel(const float* __restrict__ dout, T* __restr
 
 
 // ------------------------------------------------ windows of 65..144 tokens ---
-// Window 12 (N = 144; windows 9..11 too).  The N <= 64 kernels above keep their own dispatch; these serve
-// 64 < N <= 144 only.
+// Window 12 (N = 144; windows 9..11 too): the MFMA kernels for 64 < N <= 144.
 constexpr int NBIG = 144;              // largest window: 12 x 12
 constexpr int BR = 160;                // staged rows: 144 padded to five k-steps of 32 (rows >= N are zero)
 constexpr int KB9 = 9;                 // 16-row blocks covering 144
 constexpr int TP2 = 304;               // pitch of a [160 q][144 key] bf16 tile (288 B + 16 B)
-
-// fp32 vector kernels (any hd <= 64, both dtypes): as above with three keys (or queries) per lane,
-// lane + 64c, c < 3.  LDS [N][hd+1] fp32 images: 3 (forward) / 4 (backward) of them, 112 / 150 KB at hd 64.
-template <typename T>
-__device__ __forceinline__ void stage_win_big(float* lds, const T* base, int64_t ts, const WinGeom& g, int64_t bw,
-                                              int N, int hd, int tid) {
-  for (int idx = tid; idx < N * hd; idx += 256) {
-    const int r = idx / hd, d = idx % hd;
-    lds[r * (hd + 1) + d] = to_f32(base[win_token(g, bw, r) * ts + d]);
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void win_attn_fwd_big_kernel(const T* __restrict__ qkv, T* __restrict__ out,
-                                                              float* __restrict__ lse, const float* __restrict__ bias,
-                                                              const float* __restrict__ mask, WinGeom g, int H, int N,
-                                                              int hd, float scale) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int hp = hd + 1;
-  float* Qs = sm;
-  float* Ks = Qs + N * hp;
-  float* Vs = Ks + N * hp;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int64_t bw = blockIdx.x;
-  const int h = blockIdx.y;
-  const int64_t ts = (int64_t)3 * H * hd;
-  stage_win_big(Qs, qkv + h * hd, ts, g, bw, N, hd, tid);
-  stage_win_big(Ks, qkv + (H + h) * hd, ts, g, bw, N, hd, tid);
-  stage_win_big(Vs, qkv + (2 * H + h) * hd, ts, g, bw, N, hd, tid);
-  __syncthreads();
-  const float* mrow = mask ? mask + (bw % g.nW) * (int64_t)N * N : nullptr;
-  const int dl = lane < hd ? lane : 0;
-  for (int i = w; i < N; i += 4) {
-    float s[3], mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int k = lane + 64 * c;
-      s[c] = -INFINITY;
-      if (k < N) {
-        float a = 0.f;
-        for (int d = 0; d < hd; ++d) a = fmaf(Qs[i * hp + d] * scale, Ks[k * hp + d], a);
-        a += bias[((int64_t)h * N + i) * N + k];
-        if (mrow) a += mrow[i * N + k];
-        s[c] = a;
-      }
-      mx = fmaxf(mx, s[c]);
-    }
-    mx = wave_max(mx);
-    float p[3], sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      p[c] = lane + 64 * c < N ? expf(s[c] - mx) : 0.f;
-      sum += p[c];
-    }
-    sum = wave_sum(sum);
-    float acc = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int jn = min(N - 64 * c, 64);
-      for (int j = 0; j < jn; ++j) acc = fmaf(__shfl(p[c], j), Vs[(64 * c + j) * hp + dl], acc);
-    }
-    const int64_t tok = win_token(g, bw, i);
-    if (lane < hd) out[tok * H * hd + h * hd + lane] = from_f32<T>(acc / sum);
-    if (lane == 0) lse[(bw * H + h) * N + i] = mx + logf(sum);
-  }
-}
-
-// dQ, delta and d(bias): grid (R, H), workgroup (r, h) walks windows r, r + R, ... of head h and accumulates its
-// d(score) in partial row r of [R][H][N][N] (each element read and written by one thread only: deterministic)
-template <typename T>
-__global__ __launch_bounds__(256) void win_attn_bwd_dq_big_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
-                                                                 const float* __restrict__ lse,
-                                                                 const float* __restrict__ bias,
-                                                                 const float* __restrict__ mask, T* __restrict__ dqkv,
-                                                                 float* __restrict__ delta,
-                                                                 float* __restrict__ dbias_part, WinGeom g, int H,
-                                                                 int N, int hd, float scale, int64_t Bw) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int hp = hd + 1;
-  float* Qs = sm;
-  float* Ks = Qs + N * hp;
-  float* Vs = Ks + N * hp;
-  float* dOs = Vs + N * hp;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int h = blockIdx.y;
-  const int64_t ts = (int64_t)3 * H * hd, os = (int64_t)H * hd;
-  const int dl = lane < hd ? lane : 0;
-  float* part = dbias_part + ((int64_t)blockIdx.x * H + h) * N * N;
-  for (int64_t bw = blockIdx.x; bw < Bw; bw += gridDim.x) {
-    const bool first = bw == (int64_t)blockIdx.x;
-    __syncthreads();                               // the previous window's LDS reads are done
-    stage_win_big(Qs, qkv + h * hd, ts, g, bw, N, hd, tid);
-    stage_win_big(Ks, qkv + (H + h) * hd, ts, g, bw, N, hd, tid);
-    stage_win_big(Vs, qkv + (2 * H + h) * hd, ts, g, bw, N, hd, tid);
-    stage_win_big(dOs, dout + h * hd, os, g, bw, N, hd, tid);
-    __syncthreads();
-    const float* mrow = mask ? mask + (bw % g.nW) * (int64_t)N * N : nullptr;
-    for (int i = w; i < N; i += 4) {
-      const float l = lse[(bw * H + h) * N + i];
-      float p[3], dp[3], pd = 0.f;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int k = lane + 64 * c;
-        p[c] = 0.f;
-        dp[c] = 0.f;
-        if (k < N) {
-          float s = 0.f, e = 0.f;
-          for (int d = 0; d < hd; ++d) {
-            s = fmaf(Qs[i * hp + d] * scale, Ks[k * hp + d], s);
-            e = fmaf(dOs[i * hp + d], Vs[k * hp + d], e);
-          }
-          s += bias[((int64_t)h * N + i) * N + k];
-          if (mrow) s += mrow[i * N + k];
-          p[c] = expf(s - l);
-          dp[c] = e;
-        }
-        pd = fmaf(p[c], dp[c], pd);
-      }
-      const float del = wave_sum(pd);
-      float ds[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int k = lane + 64 * c;
-        ds[c] = p[c] * (dp[c] - del);
-        if (k < N) part[i * N + k] = first ? ds[c] : part[i * N + k] + ds[c];
-      }
-      if (lane == 0) delta[(bw * H + h) * N + i] = del;
-      float acc = 0.f;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int jn = min(N - 64 * c, 64);
-        for (int j = 0; j < jn; ++j) acc = fmaf(__shfl(ds[c], j), Ks[(64 * c + j) * hp + dl], acc);
-      }
-      if (lane < hd) dqkv[win_token(g, bw, i) * ts + h * hd + lane] = from_f32<T>(acc * scale);
-    }
-  }
-}
-
-// dK, dV: wave per key row, lanes = queries lane + 64c
-template <typename T>
-__global__ __launch_bounds__(256) void win_attn_bwd_dkdv_big_kernel(const T* __restrict__ qkv,
-                                                                   const T* __restrict__ dout,
-                                                                   const float* __restrict__ lse,
-                                                                   const float* __restrict__ delta,
-                                                                   const float* __restrict__ bias,
-                                                                   const float* __restrict__ mask,
-                                                                   T* __restrict__ dqkv, WinGeom g, int H, int N,
-                                                                   int hd, float scale) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int hp = hd + 1;
-  float* Qs = sm;
-  float* Ks = Qs + N * hp;
-  float* Vs = Ks + N * hp;
-  float* dOs = Vs + N * hp;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int64_t bw = blockIdx.x;
-  const int h = blockIdx.y;
-  const int64_t ts = (int64_t)3 * H * hd, os = (int64_t)H * hd;
-  stage_win_big(Qs, qkv + h * hd, ts, g, bw, N, hd, tid);
-  stage_win_big(Ks, qkv + (H + h) * hd, ts, g, bw, N, hd, tid);
-  stage_win_big(Vs, qkv + (2 * H + h) * hd, ts, g, bw, N, hd, tid);
-  stage_win_big(dOs, dout + h * hd, os, g, bw, N, hd, tid);
-  __syncthreads();
-  const float* mrow = mask ? mask + (bw % g.nW) * (int64_t)N * N : nullptr;
-  const int dl = lane < hd ? lane : 0;
-  for (int j = w; j < N; j += 4) {
-    float p[3], ds[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int i = lane + 64 * c;                 // query
-      p[c] = 0.f;
-      ds[c] = 0.f;
-      if (i < N) {
-        float s = 0.f, dp = 0.f;
-        for (int d = 0; d < hd; ++d) {
-          s = fmaf(Qs[i * hp + d] * scale, Ks[j * hp + d], s);
-          dp = fmaf(dOs[i * hp + d], Vs[j * hp + d], dp);
-        }
-        s += bias[((int64_t)h * N + i) * N + j];
-        if (mrow) s += mrow[i * N + j];
-        p[c] = expf(s - lse[(bw * H + h) * N + i]);
-        ds[c] = p[c] * (dp - delta[(bw * H + h) * N + i]);
-      }
-    }
-    float ak = 0.f, av = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int in = min(N - 64 * c, 64);
-      for (int i = 0; i < in; ++i) {
-        ak = fmaf(__shfl(ds[c], i), Qs[(64 * c + i) * hp + dl], ak);
-        av = fmaf(__shfl(p[c], i), dOs[(64 * c + i) * hp + dl], av);
-      }
-    }
-    if (lane < hd) {
-      T* row = dqkv + win_token(g, bw, j) * ts + h * hd + lane;
-      row[H * hd] = from_f32<T>(ak * scale);
-      row[2 * H * hd] = from_f32<T>(av);
-    }
-  }
-}
 
 // win_token / win_row_frag with the window size a compile-time constant (N = WS * WS): the per-row
 // divisions fold to multiplies and are cheap enough to recompute instead of being kept live
@@ -1271,37 +1178,6 @@ __global__ __launch_bounds__(576) void win_attn_bwd_mfma144_kernel(const bf16* _
   }
 }
 
-// dtable for windows of 65..144 tokens: as relpos_scatter_kernel, but the hits (at most N <= 144 for an index
-// of models/swin.py:120-129) are compacted into ONE list in ascending position order, through a per-iteration
-// prefix of the four waves' ballot counts; summed in that order (deterministic, no atomics)
-constexpr int RP_LIST = 256;
-__global__ __launch_bounds__(256) void relpos_scatter_big_kernel(const float* __restrict__ dbias,
-                                                                const int64_t* __restrict__ index,
-                                                                float* __restrict__ dtable, int T, int H, int NN) {
-  __shared__ int list[RP_LIST];
-  __shared__ int cnt[4];
-  const int t = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int total = 0;
-  for (int base = 0; base < NN; base += 256) {
-    const int ij = base + threadIdx.x;
-    const bool hit = ij < NN && index[ij] == t;
-    const unsigned long long m = __ballot(hit);
-    if (lane == 0) cnt[w] = __popcll(m);
-    __syncthreads();
-    int pos = total + __popcll(m & ((1ull << lane) - 1ull));
-    for (int v = 0; v < w; ++v) pos += cnt[v];
-    if (hit && pos < RP_LIST) list[pos] = ij;
-    total += cnt[0] + cnt[1] + cnt[2] + cnt[3];
-    __syncthreads();
-  }
-  const int c = min(total, RP_LIST);
-  for (int h = threadIdx.x; h < H; h += 256) {
-    float s = 0.f;
-    for (int e = 0; e < c; ++e) s += dbias[(int64_t)h * NN + list[e]];
-    dtable[(int64_t)t * H + h] = s;
-  }
-}
-
 }  // namespace
 
 static std::atomic<int> g_win_mfma{-1};   // diagnostic / test hook: 0 = fp32 vector kernels only, else MFMA where it applies
@@ -1315,29 +1191,16 @@ static int win_check(int64_t Bw, int64_t H, int64_t N, int64_t hd, int64_t Himg,
   return 0;
 }
 
-// windows of 65..144 tokens
-static int win_attn_fwd_big(const void* qkv, void* out, float* lse, const float* bias, const float* mask, int dtype,
-                            int64_t Bw, int64_t H, int64_t N, int64_t hd, const WinGeom& g, float scale,
-                            hipStream_t stream) {
-  if (dtype == VITMI_BF16 && hd == 32 && g_win_mfma != 0 && is_aligned(qkv, 16) && is_aligned(out, 8)) {
-    auto kern = N == 81 ? win_attn_fwd_mfma144_kernel<81> : N == 100 ? win_attn_fwd_mfma144_kernel<100>
-              : N == 121 ? win_attn_fwd_mfma144_kernel<121> : win_attn_fwd_mfma144_kernel<144>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(Bw * H)), dim3(64 * F144_WAVES), 0, stream,
-                       (const bf16*)qkv, (bf16*)out, lse, bias, mask, g, (int)H, scale);
-    return vitmi_check_launch("win_attn_fwd_mfma144_kernel");
-  }
-  dim3 grid((unsigned)Bw, (unsigned)H);
-  const size_t lds = 3 * N * (hd + 1) * sizeof(float);
-  const int lds_max = 3 * NBIG * 65 * sizeof(float);
+// the fp32 vector forward: C = 1 (N <= 64) or C = 3; only C = 3 can need more LDS than the default limit
+template <typename T>
+static int launch_vec_fwd(const void* qkv, void* out, float* lse, const float* bias, const float* mask, int64_t Bw,
+                          int64_t H, int64_t N, int64_t hd, const WinGeom& g, float scale, hipStream_t stream) {
+  auto kern = N > 64 ? win_attn_fwd_kernel<T, 3> : win_attn_fwd_kernel<T, 1>;
   int rc;
-  if (dtype == VITMI_BF16) {
-    if ((rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(win_attn_fwd_big_kernel<bf16>), lds_max, "win_attn_fwd"))) return rc;
-    hipLaunchKernelGGL((win_attn_fwd_big_kernel<bf16>), grid, dim3(256), lds, stream, (const bf16*)qkv, (bf16*)out, lse, bias, mask, g, (int)H, (int)N, (int)hd, scale);
-  } else if (dtype == VITMI_F32) {
-    if ((rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(win_attn_fwd_big_kernel<float>), lds_max, "win_attn_fwd"))) return rc;
-    hipLaunchKernelGGL((win_attn_fwd_big_kernel<float>), grid, dim3(256), lds, stream, (const float*)qkv, (float*)out, lse, bias, mask, g, (int)H, (int)N, (int)hd, scale);
-  } else return vitmi_fail(VITMI_E_DTYPE, "win_attn_fwd: bad dtype");
-  return vitmi_check_launch("win_attn_fwd_big_kernel");
+  if (N > 64 && (rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(kern), 3 * NBIG * 65 * sizeof(float), "win_attn_fwd"))) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)Bw, (unsigned)H), dim3(256), 3 * N * (hd + 1) * sizeof(float), stream,
+                     (const T*)qkv, (T*)out, lse, bias, mask, g, (int)H, (int)N, (int)hd, scale);
+  return vitmi_check_launch("win_attn_fwd_kernel");
 }
 
 // partial rows of the N > 64 backward: workgroups per head, each walking Bw / R windows (about one per CU in all)
@@ -1355,21 +1218,22 @@ extern "C" int vitmi_win_attn_fwd(const void* qkv, void* out, float* lse, const 
   if (rc) return rc;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   WinGeom g{(int)Himg, (int)Wimg, (int)ws, (int)shift, (int)(Wimg / ws), (int)((Himg / ws) * (Wimg / ws))};
-  if (N > 64) return win_attn_fwd_big(qkv, out, lse, bias, mask, dtype, Bw, H, N, hd, g, scale, stream);
   if (dtype == VITMI_BF16 && hd == 32 && g_win_mfma != 0 && is_aligned(qkv, 16) && is_aligned(out, 8)) {
+    if (N > 64) {
+      auto kern = N == 81 ? win_attn_fwd_mfma144_kernel<81> : N == 100 ? win_attn_fwd_mfma144_kernel<100>
+                : N == 121 ? win_attn_fwd_mfma144_kernel<121> : win_attn_fwd_mfma144_kernel<144>;
+      hipLaunchKernelGGL(kern, dim3((unsigned)(Bw * H)), dim3(64 * F144_WAVES), 0, stream,
+                         (const bf16*)qkv, (bf16*)out, lse, bias, mask, g, (int)H, scale);
+      return vitmi_check_launch("win_attn_fwd_mfma144_kernel");
+    }
     const int64_t tasks = Bw * H;
     hipLaunchKernelGGL(win_attn_fwd_mfma_kernel, dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, stream,
                        (const bf16*)qkv, (bf16*)out, lse, bias, mask, g, (int)H, (int)N, scale, tasks);
     return vitmi_check_launch("win_attn_fwd_mfma_kernel");
   }
-  dim3 grid((unsigned)Bw, (unsigned)H);
-  const size_t lds = 3 * 64 * (hd + 1) * sizeof(float);
-  if (dtype == VITMI_BF16)
-    hipLaunchKernelGGL((win_attn_fwd_kernel<bf16>), grid, dim3(256), lds, stream, (const bf16*)qkv, (bf16*)out, lse, bias, mask, g, (int)H, (int)N, (int)hd, scale);
-  else if (dtype == VITMI_F32)
-    hipLaunchKernelGGL((win_attn_fwd_kernel<float>), grid, dim3(256), lds, stream, (const float*)qkv, (float*)out, lse, bias, mask, g, (int)H, (int)N, (int)hd, scale);
-  else return vitmi_fail(VITMI_E_DTYPE, "win_attn_fwd: bad dtype");
-  return vitmi_check_launch("win_attn_fwd_kernel");
+  if (dtype == VITMI_BF16) return launch_vec_fwd<bf16>(qkv, out, lse, bias, mask, Bw, H, N, hd, g, scale, stream);
+  if (dtype == VITMI_F32) return launch_vec_fwd<float>(qkv, out, lse, bias, mask, Bw, H, N, hd, g, scale, stream);
+  return vitmi_fail(VITMI_E_DTYPE, "win_attn_fwd: bad dtype");
 }
 
 extern "C" size_t vitmi_win_attn_bwd_workspace(int64_t Bw, int64_t H, int64_t N) {
@@ -1389,40 +1253,30 @@ extern "C" int vitmi_win_attn_bwd_fuses_qkv_bias(int dtype, int64_t hd) {
   return dtype == VITMI_BF16 && hd == 32 && g_win_mfma != 0 ? 1 : 0;
 }
 
-static int win_attn_bwd_big(const void* qkv, const void* dout, const float* lse, const float* bias, const float* mask,
-                            void* dqkv, float* dbias, float* dqkv_bias, int dtype, int64_t Bw, int64_t H, int64_t N,
-                            int64_t hd, const WinGeom& g, float scale, float* delta, float* part, hipStream_t stream) {
-  const int64_t R = win_big_rows(Bw, H);
-  int rc;
-  if (dtype == VITMI_BF16 && hd == 32 && g_win_mfma != 0 && is_aligned(qkv, 16) && is_aligned(dout, 16) && is_aligned(dqkv, 8)) {
-    auto kern = N == 81 ? win_attn_bwd_mfma144_kernel<81> : N == 100 ? win_attn_bwd_mfma144_kernel<100>
-              : N == 121 ? win_attn_bwd_mfma144_kernel<121> : win_attn_bwd_mfma144_kernel<144>;
-    if ((rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(kern), B144_LDS, "win_attn_bwd"))) return rc;
-    float* qb_part = dqkv_bias ? part + R * H * N * N : nullptr;     // [R][3*H*32]
-    hipLaunchKernelGGL(kern, dim3((unsigned)(R * H)), dim3(64 * B144_WAVES), B144_LDS, stream, (const bf16*)qkv,
-                       (const bf16*)dout, lse, bias, mask, (bf16*)dqkv, part, qb_part, g, (int)H, scale, Bw, (int)R);
-    if ((rc = vitmi_check_launch("win_attn_bwd_mfma144_kernel"))) return rc;
-    if ((rc = vitmi_reduce_rows(part, (int)R, H * N * N, H * N * N, dbias, stream))) return rc;
-    if (dqkv_bias) return vitmi_reduce_rows(qb_part, (int)R, 3 * H * 32, 3 * H * 32, dqkv_bias, stream);
-    return 0;
-  }
-  VITMI_REQUIRE(!dqkv_bias, VITMI_E_DTYPE, "win_attn_bwd: dqkv_bias is produced by the bf16 hd = 32 kernel only (ask vitmi_win_attn_bwd_fuses_qkv_bias)");
+// the fp32 vector backward: dQ with its d(bias) partials in R rows (N <= 64: one row per window), then dK / dV, then
+// the deterministic reduction of the partial d(score) tiles: rows = R, cols = H*N*N
+template <typename T>
+static int launch_vec_bwd(const void* qkv, const void* dout, const float* lse, const float* bias, const float* mask,
+                          void* dqkv, float* dbias, int64_t Bw, int64_t H, int64_t N, int64_t hd, const WinGeom& g,
+                          float scale, float* delta, float* part, hipStream_t stream) {
+  auto dkdv = N > 64 ? win_attn_bwd_dkdv_kernel<T, 3> : win_attn_bwd_dkdv_kernel<T, 1>;
+  const int64_t R = N > 64 ? win_big_rows(Bw, H) : Bw;
   const size_t lds = 4 * N * (hd + 1) * sizeof(float);
   const int lds_max = 4 * NBIG * 65 * sizeof(float);
-  if (dtype == VITMI_BF16) {
-    if ((rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(win_attn_bwd_dq_big_kernel<bf16>), lds_max, "win_attn_bwd"))) return rc;
-    if ((rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(win_attn_bwd_dkdv_big_kernel<bf16>), lds_max, "win_attn_bwd"))) return rc;
-    hipLaunchKernelGGL((win_attn_bwd_dq_big_kernel<bf16>), dim3((unsigned)R, (unsigned)H), dim3(256), lds, stream, (const bf16*)qkv, (const bf16*)dout, lse, bias, mask, (bf16*)dqkv, delta, part, g, (int)H, (int)N, (int)hd, scale, Bw);
-    if ((rc = vitmi_check_launch("win_attn_bwd_dq_big_kernel"))) return rc;
-    hipLaunchKernelGGL((win_attn_bwd_dkdv_big_kernel<bf16>), dim3((unsigned)Bw, (unsigned)H), dim3(256), lds, stream, (const bf16*)qkv, (const bf16*)dout, lse, delta, bias, mask, (bf16*)dqkv, g, (int)H, (int)N, (int)hd, scale);
-  } else if (dtype == VITMI_F32) {
-    if ((rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(win_attn_bwd_dq_big_kernel<float>), lds_max, "win_attn_bwd"))) return rc;
-    if ((rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(win_attn_bwd_dkdv_big_kernel<float>), lds_max, "win_attn_bwd"))) return rc;
-    hipLaunchKernelGGL((win_attn_bwd_dq_big_kernel<float>), dim3((unsigned)R, (unsigned)H), dim3(256), lds, stream, (const float*)qkv, (const float*)dout, lse, bias, mask, (float*)dqkv, delta, part, g, (int)H, (int)N, (int)hd, scale, Bw);
-    if ((rc = vitmi_check_launch("win_attn_bwd_dq_big_kernel"))) return rc;
-    hipLaunchKernelGGL((win_attn_bwd_dkdv_big_kernel<float>), dim3((unsigned)Bw, (unsigned)H), dim3(256), lds, stream, (const float*)qkv, (const float*)dout, lse, delta, bias, mask, (float*)dqkv, g, (int)H, (int)N, (int)hd, scale);
-  } else return vitmi_fail(VITMI_E_DTYPE, "win_attn_bwd: bad dtype");
-  if ((rc = vitmi_check_launch("win_attn_bwd_dkdv_big_kernel"))) return rc;
+  int rc;
+  if (N > 64) {
+    if ((rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(win_attn_bwd_dq_big_kernel<T>), lds_max, "win_attn_bwd"))) return rc;
+    if ((rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(dkdv), lds_max, "win_attn_bwd"))) return rc;
+    hipLaunchKernelGGL((win_attn_bwd_dq_big_kernel<T>), dim3((unsigned)R, (unsigned)H), dim3(256), lds, stream, (const T*)qkv,
+                       (const T*)dout, lse, bias, mask, (T*)dqkv, delta, part, g, (int)H, (int)N, (int)hd, scale, Bw);
+  } else {
+    hipLaunchKernelGGL((win_attn_bwd_dq_kernel<T>), dim3((unsigned)R, (unsigned)H), dim3(256), lds, stream, (const T*)qkv,
+                       (const T*)dout, lse, bias, mask, (T*)dqkv, delta, part, g, (int)H, (int)N, (int)hd, scale);
+  }
+  if ((rc = vitmi_check_launch("win_attn_bwd_dq_kernel"))) return rc;
+  hipLaunchKernelGGL(dkdv, dim3((unsigned)Bw, (unsigned)H), dim3(256), lds, stream, (const T*)qkv, (const T*)dout, lse,
+                     delta, bias, mask, (T*)dqkv, g, (int)H, (int)N, (int)hd, scale);
+  if ((rc = vitmi_check_launch("win_attn_bwd_dkdv_kernel"))) return rc;
   return vitmi_reduce_rows(part, (int)R, H * N * N, H * N * N, dbias, stream);
 }
 
@@ -1439,9 +1293,20 @@ extern "C" int vitmi_win_attn_bwd(const void* qkv, const void* dout, const float
   WinGeom g{(int)Himg, (int)Wimg, (int)ws, (int)shift, (int)(Wimg / ws), (int)((Himg / ws) * (Wimg / ws))};
   float* delta = reinterpret_cast<float*>(workspace);
   float* part = delta + Bw * H * N;
-  if (N > 64) return win_attn_bwd_big(qkv, dout, lse, bias, mask, dqkv, dbias, dqkv_bias, dtype, Bw, H, N, hd, g, scale,
-                                      delta, part, stream);
   if (dtype == VITMI_BF16 && hd == 32 && g_win_mfma != 0 && is_aligned(qkv, 16) && is_aligned(dout, 16) && is_aligned(dqkv, 8)) {
+    if (N > 64) {
+      const int64_t R = win_big_rows(Bw, H);
+      auto kern = N == 81 ? win_attn_bwd_mfma144_kernel<81> : N == 100 ? win_attn_bwd_mfma144_kernel<100>
+                : N == 121 ? win_attn_bwd_mfma144_kernel<121> : win_attn_bwd_mfma144_kernel<144>;
+      if ((rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(kern), B144_LDS, "win_attn_bwd"))) return rc;
+      float* qb_part = dqkv_bias ? part + R * H * N * N : nullptr;     // [R][3*H*32]
+      hipLaunchKernelGGL(kern, dim3((unsigned)(R * H)), dim3(64 * B144_WAVES), B144_LDS, stream, (const bf16*)qkv,
+                         (const bf16*)dout, lse, bias, mask, (bf16*)dqkv, part, qb_part, g, (int)H, scale, Bw, (int)R);
+      if ((rc = vitmi_check_launch("win_attn_bwd_mfma144_kernel"))) return rc;
+      if ((rc = vitmi_reduce_rows(part, (int)R, H * N * N, H * N * N, dbias, stream))) return rc;
+      if (dqkv_bias) return vitmi_reduce_rows(qb_part, (int)R, 3 * H * 32, 3 * H * 32, dqkv_bias, stream);
+      return 0;
+    }
     // one head per wave, ~4 waves per CU; nwaves a multiple of H, at most one wave per task
     int64_t per_head = 1024 / H;
     if (per_head > Bw) per_head = Bw;
@@ -1459,20 +1324,9 @@ extern "C" int vitmi_win_attn_bwd(const void* qkv, const void* dout, const float
     return 0;
   }
   VITMI_REQUIRE(!dqkv_bias, VITMI_E_DTYPE, "win_attn_bwd: dqkv_bias is produced by the bf16 hd = 32 kernel only (ask vitmi_win_attn_bwd_fuses_qkv_bias)");
-  dim3 grid((unsigned)Bw, (unsigned)H);
-  const size_t lds = 4 * 64 * (hd + 1) * sizeof(float);
-  if (dtype == VITMI_BF16) {
-    hipLaunchKernelGGL((win_attn_bwd_dq_kernel<bf16>), grid, dim3(256), lds, stream, (const bf16*)qkv, (const bf16*)dout, lse, bias, mask, (bf16*)dqkv, delta, part, g, (int)H, (int)N, (int)hd, scale);
-    if ((rc = vitmi_check_launch("win_attn_bwd_dq_kernel"))) return rc;
-    hipLaunchKernelGGL((win_attn_bwd_dkdv_kernel<bf16>), grid, dim3(256), lds, stream, (const bf16*)qkv, (const bf16*)dout, lse, delta, bias, mask, (bf16*)dqkv, g, (int)H, (int)N, (int)hd, scale);
-  } else if (dtype == VITMI_F32) {
-    hipLaunchKernelGGL((win_attn_bwd_dq_kernel<float>), grid, dim3(256), lds, stream, (const float*)qkv, (const float*)dout, lse, bias, mask, (float*)dqkv, delta, part, g, (int)H, (int)N, (int)hd, scale);
-    if ((rc = vitmi_check_launch("win_attn_bwd_dq_kernel"))) return rc;
-    hipLaunchKernelGGL((win_attn_bwd_dkdv_kernel<float>), grid, dim3(256), lds, stream, (const float*)qkv, (const float*)dout, lse, delta, bias, mask, (float*)dqkv, g, (int)H, (int)N, (int)hd, scale);
-  } else return vitmi_fail(VITMI_E_DTYPE, "win_attn_bwd: bad dtype");
-  if ((rc = vitmi_check_launch("win_attn_bwd_dkdv_kernel"))) return rc;
-  // deterministic reduction of the per-window d(score) tiles: rows = windows, cols = H*N*N
-  return vitmi_reduce_rows(part, (int)Bw, H * N * N, H * N * N, dbias, stream);
+  if (dtype == VITMI_BF16) return launch_vec_bwd<bf16>(qkv, dout, lse, bias, mask, dqkv, dbias, Bw, H, N, hd, g, scale, delta, part, stream);
+  if (dtype == VITMI_F32) return launch_vec_bwd<float>(qkv, dout, lse, bias, mask, dqkv, dbias, Bw, H, N, hd, g, scale, delta, part, stream);
+  return vitmi_fail(VITMI_E_DTYPE, "win_attn_bwd: bad dtype");
 }
 
 extern "C" void vitmi_debug_win_bwd_prefetch(int on) { g_win_bwd_prefetch = on; }
@@ -1490,10 +1344,6 @@ extern "C" int vitmi_relpos_bias(const float* table, const int64_t* index, float
     if (rc) return rc;
   }
   if (dbias && dtable) {
-    if (N > 64) {
-      hipLaunchKernelGGL(relpos_scatter_big_kernel, dim3((unsigned)T), dim3(256), 0, stream, dbias, index, dtable, (int)T, (int)H, NN);
-      return vitmi_check_launch("relpos_scatter_big_kernel");
-    }
     hipLaunchKernelGGL(relpos_scatter_kernel, dim3((unsigned)T), dim3(256), 0, stream, dbias, index, dtable, (int)T, (int)H, NN);
     return vitmi_check_launch("relpos_scatter_kernel");
   }
