@@ -672,12 +672,18 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const bf16* __restrict
         const bf16x8 a = *reinterpret_cast<const bf16x8*>(Vl + (sb * 32 + lr) * KS + (16 * ks + 8 * h5) * 2);
         dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, dof[ks], dpt, 0, 0, 0);
       }
-      // zero-filled K/V rows (key >= N) give a finite p and dS that multiply a zero
-      // K^T row below, so no masking is needed
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float p = __builtin_amdgcn_exp2f(fmaf(st[r], scale_log2e, -lse_q));
         st[r] = p * (dpt[r] - del_q);
+      }
+      // zero-filled K/V rows (key >= N) multiply a zero K^T row below, but their p = exp(-lse) overflows
+      // when lse < -88 and inf * 0 is NaN: dS of those keys is zeroed, in the ragged block only
+      const int key0 = c * CK + sb * 32;
+      if (key0 + 32 > N) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (key0 + mfma32_row(r, h5) >= N) st[r] = 0.f;
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
