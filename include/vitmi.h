@@ -241,6 +241,25 @@ int vitmi_attn_bwd(const void* qkv, const void* out, const void* dout,
                    float* dbias_part, int32_t launch_flags,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ XCA --
+ * XCiT's cross-covariance attention (models/xcit.py:237-257): attention over channels.  Per (image, head), with
+ * Q, K, V [N, hd] the head's slices of qkv [B, N, 3, H, hd] (as vitmi_attn_fwd reads it) and tau = temperature[h]:
+ *   r_q[i] = max(|Q[:, i]|_2, 1e-12), r_k likewise;  Gh = (Q^T K) / (r_q r_k^T);  A = softmax_j(tau Gh);
+ *   out[b, n, h*hd + i] = sum_j A[i][j] V[n][j]     ([B, N, H*hd], ready for the proj Linear).
+ * stat, fp32 [B, H, hd+2, hd], is all the forward keeps: rows 0..hd-1 Gh, row hd r_q, row hd+1 r_k.  The backward takes
+ * dout [B, N, H*hd] and writes dqkv [B, N, 3, H, hd] and dtemp_part, fp32 [B, H]: its column sums (vitmi_colsum) are the
+ * temperature gradient.  No atomics: every output is bitwise repeatable.  bf16 (matrix pipe, fp32 accumulation; A and
+ * M = dGh / (r_q r_k) are rounded to bf16 before the token-sized products) or fp32; hd in {32, 48, 64}, any H >= 1 and
+ * N >= 1.  qkv, out, stat, dout, dqkv 16-byte aligned.  Anything else fails before any launch.  The workspace may be
+ * null (vitmi_xca_workspace is 0 today).  Additive to ABI 109. */
+int vitmi_xca_supported(int dtype, int64_t H, int64_t N, int64_t hd);
+size_t vitmi_xca_workspace(int64_t B, int64_t H, int64_t N, int64_t hd);
+int vitmi_xca_fwd(const void* qkv, const float* temperature, void* out, float* stat, int dtype,
+                  int64_t B, int64_t N, int64_t H, int64_t hd, void* workspace, size_t workspace_bytes, void* stream);
+int vitmi_xca_bwd(const void* qkv, const void* dout, const float* temperature, const float* stat,
+                  void* dqkv, float* dtemp_part, int dtype,
+                  int64_t B, int64_t N, int64_t H, int64_t hd, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------- CaiT ops --
  * Talking-heads softmax (models/cait.py:118-122) on score tensors [B,H,N,ld] (row length
  * Nk <= 1024 valid columns, H <= 16; other shapes fail with VITMI_E_SHAPE before any launch):

@@ -87,6 +87,10 @@ SIGNATURES = {
     "vitmi_fold_many": (C.c_int, [C.POINTER(FoldDesc), C.c_int, c_vp]),
     "vitmi_attn_fwd": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, c_i64, c_i64, c_i64, c_i64, c_f32, c_vp]),
     "vitmi_attn_probs": (C.c_int, [c_vp, c_vp, C.c_int, c_i64, c_i64, c_i64, c_i64, c_f32, c_vp]),
+    "vitmi_xca_supported": (C.c_int, [C.c_int, c_i64, c_i64, c_i64]),
+    "vitmi_xca_workspace": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "vitmi_xca_fwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_sz, c_vp]),
+    "vitmi_xca_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_sz, c_vp]),
     "vitmi_attn_bwd_workspace": (c_sz, [c_i64, c_i64, c_i64]),
     "vitmi_attn_bwd_dbias_rows": (c_i64, [c_i64, c_i64]),
     "vitmi_attn_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_i64, c_i64, c_i64, c_i64,

@@ -38,6 +38,7 @@ SOURCES = [
     "attention.hip",
     "attention_f32.hip",
     "attn_probs.hip",
+    "xca.hip",
     "cait_ops.hip",
     "cait_fused.hip",
     "swin_ops.hip",

@@ -346,6 +346,69 @@ def attn_probs(qkv, P, B, N, H, hd, scale):
     return P
 
 
+def xca_supported(t, H, N, hd) -> bool:
+    """Host-only query: do the cross-covariance attention kernels (xca_fwd / xca_bwd) take this dtype and shape?"""
+    code = (BF16 if t == torch.bfloat16 else F32 if t == torch.float32 else -1) if isinstance(t, torch.dtype) else \
+        (BF16 if t.dtype == torch.bfloat16 else F32 if t.dtype == torch.float32 else -1)
+    return bool(load().vitmi_xca_supported(code, H, N, hd))
+
+
+def _xca_check(who, qkv, temperature, B, N, H, hd):
+    if qkv.dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.VitmiError(f"{who}: qkv must be bf16 or fp32, got {qkv.dtype}")
+    if not qkv.is_contiguous() or qkv.numel() != B * N * 3 * H * hd:
+        raise _lib.VitmiError(f"{who}: qkv must be a contiguous [B*N, 3*H*hd] = [{B * N}, {3 * H * hd}] tensor "
+                              f"(got {tuple(qkv.shape)})")
+    if temperature.dtype != torch.float32 or not temperature.is_contiguous() or temperature.numel() != H:
+        raise _lib.VitmiError(f"{who}: temperature must be a contiguous fp32 tensor of H = {H} elements "
+                              f"(got {temperature.dtype}, {tuple(temperature.shape)})")
+
+
+def _xca_like(who, name, t, dtype, numel, shape):
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() != numel:
+        raise _lib.VitmiError(f"{who}: {name} must be a contiguous {dtype} {shape} tensor (got {t.dtype}, {tuple(t.shape)})")
+
+
+def _xca_ws(B, H, N, hd, device):
+    need = load().vitmi_xca_workspace(B, H, N, hd)
+    if not need:
+        return None, 0
+    w = workspace(need + 256, device)
+    off = (-w.data_ptr()) % 256
+    return w.data_ptr() + off, w.numel() - off
+
+
+def xca_fwd(qkv, temperature, out, stat, B, N, H, hd):
+    """out [B, N, H*hd] = XCiT's cross-covariance attention of qkv [B*N, 3*H*hd] (bf16 or fp32, as attn_fwd reads it) with
+    the per-head fp32 temperature [H]; stat fp32 [B, H, hd+2, hd] (normalised covariance and both norm rows) is what
+    xca_bwd needs besides qkv (vitmi_xca_fwd).  hd in {32, 48, 64}."""
+    _need_cuda(qkv, temperature, out, stat)
+    _xca_check("xca_fwd", qkv, temperature, B, N, H, hd)
+    _xca_like("xca_fwd", "out", out, qkv.dtype, B * N * H * hd, f"[B, N, H*hd] = [{B}, {N}, {H * hd}]")
+    _xca_like("xca_fwd", "stat", stat, torch.float32, B * H * (hd + 2) * hd, f"[B, H, hd+2, hd] = [{B}, {H}, {hd + 2}, {hd}]")
+    ptr, nb = _xca_ws(B, H, N, hd, qkv.device)
+    check(load().vitmi_xca_fwd(qkv.data_ptr(), temperature.data_ptr(), out.data_ptr(), stat.data_ptr(), dtype_code(qkv),
+                               B, N, H, hd, ptr, nb, _stream()), "vitmi_xca_fwd")
+    return out
+
+
+def xca_bwd(qkv, dout, temperature, stat, dqkv, dtemp, B, N, H, hd):
+    """Backward of xca_fwd: dqkv [B*N, 3*H*hd] and dtemp fp32 [H] from dout [B, N, H*hd] (vitmi_xca_bwd writes one
+    temperature partial per (image, head); their batch sum is a colsum)."""
+    _need_cuda(qkv, dout, temperature, stat, dqkv, dtemp)
+    _xca_check("xca_bwd", qkv, temperature, B, N, H, hd)
+    _xca_like("xca_bwd", "dout", dout, qkv.dtype, B * N * H * hd, f"[B, N, H*hd] = [{B}, {N}, {H * hd}]")
+    _xca_like("xca_bwd", "dqkv", dqkv, qkv.dtype, B * N * 3 * H * hd, f"[B*N, 3*H*hd] = [{B * N}, {3 * H * hd}]")
+    _xca_like("xca_bwd", "stat", stat, torch.float32, B * H * (hd + 2) * hd, f"[B, H, hd+2, hd] = [{B}, {H}, {hd + 2}, {hd}]")
+    _xca_like("xca_bwd", "dtemp", dtemp, torch.float32, H, f"[H] = [{H}]")
+    part = torch.empty((B, H), dtype=torch.float32, device=qkv.device)
+    ptr, nb = _xca_ws(B, H, N, hd, qkv.device)
+    check(load().vitmi_xca_bwd(qkv.data_ptr(), dout.data_ptr(), temperature.data_ptr(), stat.data_ptr(), dqkv.data_ptr(),
+                               part.data_ptr(), dtype_code(qkv), B, N, H, hd, ptr, nb, _stream()), "vitmi_xca_bwd")
+    colsum(part, dtemp, M=B, N=H)
+    return dqkv
+
+
 def attn_bwd_dbias_rows(B, N) -> int:
     return int(load().vitmi_attn_bwd_dbias_rows(B, N))
 

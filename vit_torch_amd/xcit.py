@@ -1,0 +1,121 @@
+"""XCiT's cross-covariance attention (XCA) on libvitmi kernels.
+
+`XCA` is the attention module of the reference's `models/xcit.py:221-261`: a qkv Linear, attention over CHANNELS
+(q and k L2-normalised along the token axis, a learnable per-head temperature, a softmax over an hd x hd map per head)
+and a proj Linear.  It keeps the reference's parameter names and state-dict keys (`temperature [H,1,1]`, `qkv.weight`,
+`qkv.bias`, `proj.weight`, `proj.bias`), so its checkpoints load unchanged.  The rest of XCiT (LPI, ConvPatchEmbed, the
+Fourier positional encoding, an engine) is not built.
+
+A stand-alone module in the manner of `ClassifierHead`: the parameters live in a `ParamPack` (the fused optimizers
+update them), forward and backward run through one `torch.autograd.Function` on `ops.gemm`, `ops.xca_fwd` / `ops.xca_bwd`
+and `ops.colsum`.  compute_dtype "bf16": bf16 activations between the stages, GEMMs on the pack's bf16 weight shadows;
+"fp32": everything in fp32.  CPU tensors raise: there is no fallback.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from ._lib import VitmiError
+from .engine import param_grads
+from .packing import ParamPack
+
+
+class _XcaFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mod, x, *params):
+        ctx.mod = mod
+        ctx.need_dx = x.requires_grad
+        return mod._forward(x, save=True)
+
+    @staticmethod
+    def backward(ctx, dout):
+        mod = ctx.mod
+        held = mod._pack.begin_backward()       # torch's accumulation contract (packing.ParamPack.begin_backward)
+        dx = mod._backward(dout, ctx.need_dx)
+        mod._pack.end_backward(held)
+        return (None, dx, *param_grads(mod._pack))
+
+
+class XCA(nn.Module):
+    def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0., compute_dtype="bf16"):
+        super().__init__()
+        if attn_drop != 0. or proj_drop != 0.:
+            raise VitmiError("XCA: dropout is not built (the reference's XCiT factories use attn_drop = proj_drop = 0)")
+        if compute_dtype not in ("bf16", "fp32"):
+            raise VitmiError(f"XCA: compute_dtype must be 'bf16' or 'fp32', got {compute_dtype!r}")
+        if dim % num_heads or dim // num_heads not in (32, 48, 64):
+            raise VitmiError(f"XCA: head dim {dim}/{num_heads} not in {{32, 48, 64}}")
+        self.dim, self.num_heads, self.compute_dtype = dim, num_heads, compute_dtype
+        self.temperature = nn.Parameter(torch.ones(num_heads, 1, 1))
+        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
+        self.proj = nn.Linear(dim, dim)
+        self._pack = None
+        self._saved = None
+
+    def no_weight_decay(self):
+        return {"temperature"}
+
+    def engine(self):
+        """(Re)build the flat parameter buffers (after .to(device) / load_state_dict)."""
+        dev = self.temperature.device
+        if dev.type != "cuda":
+            raise VitmiError("move the module to the GPU before the first forward")
+        if self._pack is None or not self._pack.is_current() or len(self._pack.params) != sum(1 for _ in self.parameters()):
+            self._pack = ParamPack(list(self.named_parameters()), dev, shadow=self.compute_dtype == "bf16")
+        return self
+
+    @property
+    def pack(self):
+        return self.engine()._pack
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise VitmiError("vit_torch_amd.XCA runs on an MI355X (HIP) device; got a CPU tensor and there is no CPU fallback")
+        if x.dim() != 3 or x.shape[-1] != self.dim:
+            raise VitmiError(f"XCA: input must be [B, N, {self.dim}], got {tuple(x.shape)}")
+        self.engine()
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._pack.params)):
+            return _XcaFn.apply(self, x, *self._pack.params)
+        return self._forward(x, save=False)
+
+    # ---- kernels
+    def _forward(self, x, save):
+        B, N, C = x.shape
+        H, hd, pk = self.num_heads, C // self.num_heads, self._pack
+        dt = torch.bfloat16 if self.compute_dtype == "bf16" else torch.float32
+        pk.refresh_shadow()
+        xa = x.reshape(B * N, C).to(dt).contiguous()
+        qkv = torch.empty((B * N, 3 * C), dtype=dt, device=x.device)
+        ops.gemm(xa, pk.w(self.qkv.weight), qkv, bias=pk.f32(self.qkv.bias) if self.qkv.bias is not None else None)
+        att = torch.empty((B * N, C), dtype=dt, device=x.device)
+        stat = torch.empty((B, H, hd + 2, hd), dtype=torch.float32, device=x.device)
+        ops.xca_fwd(qkv, pk.f32(self.temperature).view(H), att, stat, B, N, H, hd)
+        y = torch.empty((B * N, C), dtype=torch.float32, device=x.device)
+        ops.gemm(att, pk.w(self.proj.weight), y, bias=pk.f32(self.proj.bias))
+        if save:
+            self._saved = (xa, qkv, att, stat, (B, N))
+        return y.view(B, N, C)
+
+    def _backward(self, dout, need_dx):
+        if self._saved is None:
+            raise VitmiError("backward called without a saved forward (or called twice)")
+        (xa, qkv, att, stat, (B, N)), self._saved = self._saved, None
+        C, H, pk = self.dim, self.num_heads, self._pack
+        hd, dt = C // H, xa.dtype
+        dy = dout.reshape(B * N, C).to(dt).contiguous()
+        ops.gemm(dy, att, pk.g(self.proj.weight), a_kmajor=False, b_kmajor=False)
+        ops.colsum(dy, pk.g(self.proj.bias))
+        datt = torch.empty((B * N, C), dtype=dt, device=dy.device)
+        ops.gemm(dy, pk.w(self.proj.weight), datt, b_kmajor=False)
+        dqkv = torch.empty_like(qkv)
+        ops.xca_bwd(qkv, datt, pk.f32(self.temperature).view(H), stat, dqkv, pk.g(self.temperature).view(H), B, N, H, hd)
+        ops.gemm(dqkv, xa, pk.g(self.qkv.weight), a_kmajor=False, b_kmajor=False)
+        if self.qkv.bias is not None:
+            ops.colsum(dqkv, pk.g(self.qkv.bias))
+        if not need_dx:
+            return None
+        dx = torch.empty((B * N, C), dtype=torch.float32, device=dy.device)
+        ops.gemm(dqkv, pk.w(self.qkv.weight), dx, b_kmajor=False)
+        return dx.view(B, N, C)
