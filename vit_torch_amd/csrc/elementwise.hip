@@ -347,7 +347,7 @@ __global__ void sgd_momentum_kernel(float* __restrict__ p, const float* __restri
 // ------------------------------------------------------------------ adam --
 // torch.optim.Adam / AdamW single-tensor update (decoupled decay when `decoupled`):
 //   p *= 1 - lr*wd (AdamW)  |  g += wd*p (Adam);  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
-//   p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
+//   p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)      (AdamW as ONE subtraction: p -= lr*wd*p + that)
 // The step count t lives on the DEVICE (state[0]) and is advanced by a one-thread kernel
 // before the update, so a captured HIP graph replays the right bias corrections.
 __global__ void adam_tick_kernel(float* state) { state[0] += 1.f; }
@@ -356,19 +356,22 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
                             float* __restrict__ v, bf16* __restrict__ shadow, const float* __restrict__ state,
                             int64_t n, float lr, float b1, float b2, float eps, float wd, int decoupled,
                             float gscale) {
-  const float t = state[0];
-  const float bc1 = 1.f - powf(b1, t), bc2s = sqrtf(1.f - powf(b2, t));
-  const float step = lr / bc1;
+  // the step-dependent scalars in double: 1 - b2^t formed in fp32 loses log2(1 / (1 - b2^t)) bits to the cancellation
+  // (7 at t = 7, b2 = 0.999), which put sqrt(1 - b2^t) up to 1e-5 off; once per thread, ahead of a loop that streams 22 B
+  const double t = state[0];
+  const double bc1 = 1.0 - pow((double)b1, t), bc2 = 1.0 - pow((double)b2, t);
+  const float step = (float)((double)lr / bc1), bc2s = (float)sqrt(bc2);
+  const float lrwd = decoupled ? (float)((double)lr * (double)wd) : 0.f;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float pi = p[i], gi = g[i] * gscale;
-    if (decoupled) pi *= 1.f - lr * wd;
-    else gi = fmaf(wd, pi, gi);
+    if (!decoupled) gi = fmaf(wd, pi, gi);
     const float mi = b1 * m[i] + (1.f - b1) * gi;
     const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
     m[i] = mi;
     v[i] = vi;
-    pi -= step * mi / (sqrtf(vi) / bc2s + eps);
+    // decoupled decay joins the update, p -= lr wd p + step m / denom: the parameter is rounded once, not twice
+    pi -= fmaf(lrwd, pi, step * mi / (sqrtf(vi) / bc2s + eps));
     p[i] = pi;
     if (shadow) shadow[i] = (bf16)pi;
   }
