@@ -260,6 +260,34 @@ int vitmi_xca_bwd(const void* qkv, const void* dout, const float* temperature, c
                   void* dqkv, float* dtemp_part, int dtype,
                   int64_t B, int64_t N, int64_t H, int64_t hd, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ LPI --
+ * XCiT's local patch interaction (models/xcit.py:111-141): depthwise 3x3 conv, GELU (erf), BatchNorm2d, depthwise 3x3
+ * conv on the token grid, on token-major rows x [B, H*W, C] (C contiguous); no NCHW copy.  Per channel:
+ *   u = gelu(conv1(x) + b1), stored in the compute dtype;  training: mean and biased variance of u AS STORED over all
+ *   B*H*W positions, eval: running_mean / running_var;  z = (u - mean) rstd gamma + beta;  out = conv2(z) + b2 (zero
+ *   padding of z).  w1, w2 are the parameters' own [C,1,3,3] fp32 memory viewed [C, 9]; every parameter and parameter
+ *   gradient is fp32.  _fwd writes u and stat fp32 [2, C] = (mean, rstd): all _bwd needs besides x and dout.  In training
+ *   it also updates in place, on the device: running_mean <- (1-m) running_mean + m mean, running_var <- (1-m)
+ *   running_var + m var M/(M-1), num_batches_tracked += 1 (any of the three may be null: not tracked); in eval mode no
+ *   buffer is touched.  _bwd STORES dx (compute dtype) and dw1 [C,9], db1, dgamma, dbeta, dw2 [C,9], db2 (fp32); with
+ *   training = 0 it is the eval-mode gradient (du = gamma rstd dz).  The backward stages one tensor, dc = dL/d(conv1
+ *   output), in the compute dtype in the workspace: in bf16 a declared rounding of what dx is summed from.  Statistics by
+ *   Welford / Chan in a fixed order, no atomics: every output is bitwise repeatable.  bf16 or fp32 activations; C a
+ *   multiple of 8; B, H, W >= 1 (B*H*W < 2^31); training needs B*H*W > 1.  x, u, out, dout, dx, stat and the parameters
+ *   16-byte aligned; the workspace (vitmi_lpi_workspace bytes, 16-byte aligned) is required.  Anything else fails before
+ *   any launch.  Additive to ABI 109. */
+int vitmi_lpi_supported(int dtype, int64_t B, int64_t H, int64_t W, int64_t C);
+size_t vitmi_lpi_workspace(int dtype, int64_t B, int64_t H, int64_t W, int64_t C);
+int vitmi_lpi_fwd(const void* x, const float* w1, const float* b1, const float* gamma, const float* beta,
+                  const float* w2, const float* b2, float* running_mean, float* running_var,
+                  int64_t* num_batches_tracked, void* u, float* stat, void* out, int dtype, int training,
+                  float momentum, float eps, int64_t B, int64_t H, int64_t W, int64_t C,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int vitmi_lpi_bwd(const void* x, const void* u, const void* dout, const float* stat, const float* w1, const float* b1,
+                  const float* gamma, const float* beta, const float* w2, void* dx, float* dw1, float* db1,
+                  float* dgamma, float* dbeta, float* dw2, float* db2, int dtype, int training,
+                  int64_t B, int64_t H, int64_t W, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------- CaiT ops --
  * Talking-heads softmax (models/cait.py:118-122) on score tensors [B,H,N,ld] (row length
  * Nk <= 1024 valid columns, H <= 16; other shapes fail with VITMI_E_SHAPE before any launch):

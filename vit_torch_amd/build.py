@@ -39,6 +39,7 @@ SOURCES = [
     "attention_f32.hip",
     "attn_probs.hip",
     "xca.hip",
+    "lpi.hip",
     "cait_ops.hip",
     "cait_fused.hip",
     "swin_ops.hip",

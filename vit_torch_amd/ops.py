@@ -409,6 +409,88 @@ def xca_bwd(qkv, dout, temperature, stat, dqkv, dtemp, B, N, H, hd):
     return dqkv
 
 
+def _lpi_code(t):
+    dt = t if isinstance(t, torch.dtype) else t.dtype
+    return BF16 if dt == torch.bfloat16 else F32 if dt == torch.float32 else -1
+
+
+def lpi_supported(t, B, H, W, C) -> bool:
+    """Host-only query: do the local patch interaction kernels (lpi_fwd / lpi_bwd) take this dtype and shape?"""
+    return bool(load().vitmi_lpi_supported(_lpi_code(t), B, H, W, C))
+
+
+def _lpi_act(who, name, t, dtype, B, H, W, C):
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() != B * H * W * C:
+        raise _lib.VitmiError(f"{who}: {name} must be a contiguous {dtype} [B, H*W, C] = [{B}, {H * W}, {C}] tensor "
+                              f"(got {t.dtype}, {tuple(t.shape)})")
+
+
+def _lpi_f32(who, name, t, numel):
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
+        raise _lib.VitmiError(f"{who}: {name} must be a contiguous fp32 tensor of {numel} elements "
+                              f"(got {t.dtype}, {tuple(t.shape)})")
+
+
+def _lpi_ws(code, B, H, W, C, device):
+    need = load().vitmi_lpi_workspace(code, B, H, W, C)
+    w = workspace(need + 256, device)
+    off = (-w.data_ptr()) % 256
+    return w.data_ptr() + off, w.numel() - off
+
+
+def lpi_fwd(x, w1, b1, gamma, beta, w2, b2, running_mean, running_var, num_batches_tracked, u, stat, out, B, H, W, C, *,
+            training, momentum=0.1, eps=1e-5):
+    """out [B, H*W, C] = XCiT's LPI (depthwise 3x3 conv, GELU, BatchNorm2d, depthwise 3x3 conv) of the token-major
+    x [B, H*W, C] (bf16 or fp32); fp32 parameters, the conv weights as their own [C,1,3,3] memory.  Writes u (the GELU
+    output, compute dtype) and stat fp32 [2, C] (mean, rstd), which lpi_bwd needs.  training: batch statistics, and the
+    three running buffers (fp32 [C], fp32 [C], int64 [1]; each may be None) are updated on the device; otherwise the
+    running statistics are used and nothing is touched (vitmi_lpi_fwd)."""
+    _need_cuda(x, w1, b1, gamma, beta, w2, b2, running_mean, running_var, num_batches_tracked, u, stat, out)
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.VitmiError(f"lpi_fwd: x must be bf16 or fp32, got {x.dtype}")
+    _lpi_act("lpi_fwd", "x", x, x.dtype, B, H, W, C)
+    _lpi_act("lpi_fwd", "u", u, x.dtype, B, H, W, C)
+    _lpi_act("lpi_fwd", "out", out, x.dtype, B, H, W, C)
+    for name, t, n in (("conv1.weight", w1, 9 * C), ("conv1.bias", b1, C), ("bn.weight", gamma, C), ("bn.bias", beta, C),
+                       ("conv2.weight", w2, 9 * C), ("conv2.bias", b2, C), ("stat", stat, 2 * C)):
+        _lpi_f32("lpi_fwd", name, t, n)
+    for name, t in (("running_mean", running_mean), ("running_var", running_var)):
+        if t is not None:
+            _lpi_f32("lpi_fwd", name, t, C)
+    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1):
+        raise _lib.VitmiError("lpi_fwd: num_batches_tracked must be an int64 tensor of one element")
+    if not training and (running_mean is None or running_var is None):
+        raise _lib.VitmiError("lpi_fwd: eval mode needs running_mean and running_var")
+    code = dtype_code(x)
+    ptr, nb = _lpi_ws(code, B, H, W, C, x.device)
+    check(load().vitmi_lpi_fwd(x.data_ptr(), w1.data_ptr(), b1.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w2.data_ptr(),
+                               b2.data_ptr(), _ptr(running_mean), _ptr(running_var), _ptr(num_batches_tracked), u.data_ptr(),
+                               stat.data_ptr(), out.data_ptr(), code, int(bool(training)), momentum, eps, B, H, W, C,
+                               ptr, nb, _stream()), "vitmi_lpi_fwd")
+    return out
+
+
+def lpi_bwd(x, u, dout, stat, w1, b1, gamma, beta, w2, dx, dw1, db1, dgamma, dbeta, dw2, db2, B, H, W, C, *, training):
+    """Backward of lpi_fwd: dx (compute dtype) and the six fp32 parameter gradients, stored, from dout, the saved u and stat
+    and x (vitmi_lpi_bwd); training=False is the eval-mode gradient."""
+    _need_cuda(x, u, dout, stat, w1, b1, gamma, beta, w2, dx, dw1, db1, dgamma, dbeta, dw2, db2)
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.VitmiError(f"lpi_bwd: x must be bf16 or fp32, got {x.dtype}")
+    for name, t in (("x", x), ("u", u), ("dout", dout), ("dx", dx)):
+        _lpi_act("lpi_bwd", name, t, x.dtype, B, H, W, C)
+    for name, t, n in (("stat", stat, 2 * C), ("conv1.weight", w1, 9 * C), ("conv1.bias", b1, C), ("bn.weight", gamma, C),
+                       ("bn.bias", beta, C), ("conv2.weight", w2, 9 * C), ("dw1", dw1, 9 * C), ("db1", db1, C),
+                       ("dgamma", dgamma, C), ("dbeta", dbeta, C), ("dw2", dw2, 9 * C), ("db2", db2, C)):
+        _lpi_f32("lpi_bwd", name, t, n)
+    code = dtype_code(x)
+    ptr, nb = _lpi_ws(code, B, H, W, C, x.device)
+    check(load().vitmi_lpi_bwd(x.data_ptr(), u.data_ptr(), dout.data_ptr(), stat.data_ptr(), w1.data_ptr(), b1.data_ptr(),
+                               gamma.data_ptr(), beta.data_ptr(), w2.data_ptr(), dx.data_ptr(), dw1.data_ptr(), db1.data_ptr(),
+                               dgamma.data_ptr(), dbeta.data_ptr(), dw2.data_ptr(), db2.data_ptr(), code, int(bool(training)),
+                               B, H, W, C, ptr, nb, _stream()), "vitmi_lpi_bwd")
+    return dx
+
+
 def attn_bwd_dbias_rows(B, N) -> int:
     return int(load().vitmi_attn_bwd_dbias_rows(B, N))
 

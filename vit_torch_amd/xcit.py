@@ -1,15 +1,23 @@
-"""XCiT's cross-covariance attention (XCA) on libvitmi kernels.
+"""XCiT's cross-covariance attention (XCA) and local patch interaction (LPI) on libvitmi kernels.
 
 `XCA` is the attention module of the reference's `models/xcit.py:221-261`: a qkv Linear, attention over CHANNELS
 (q and k L2-normalised along the token axis, a learnable per-head temperature, a softmax over an hd x hd map per head)
 and a proj Linear.  It keeps the reference's parameter names and state-dict keys (`temperature [H,1,1]`, `qkv.weight`,
-`qkv.bias`, `proj.weight`, `proj.bias`), so its checkpoints load unchanged.  The rest of XCiT (LPI, ConvPatchEmbed, the
-Fourier positional encoding, an engine) is not built.
+`qkv.bias`, `proj.weight`, `proj.bias`), so its checkpoints load unchanged.
 
-A stand-alone module in the manner of `ClassifierHead`: the parameters live in a `ParamPack` (the fused optimizers
-update them), forward and backward run through one `torch.autograd.Function` on `ops.gemm`, `ops.xca_fwd` / `ops.xca_bwd`
-and `ops.colsum`.  compute_dtype "bf16": bf16 activations between the stages, GEMMs on the pack's bf16 weight shadows;
-"fp32": everything in fp32.  CPU tensors raise: there is no fallback.
+`LPI` is the reference's `models/xcit.py:111-141`: depthwise 3x3 conv, GELU, BatchNorm2d (`SyncBatchNorm` there), depthwise
+3x3 conv on the token grid, as one fused op each way on the token-major `[B, H*W, C]` tensor (`ops.lpi_fwd` / `ops.lpi_bwd`,
+`lpi.hip`): no NCHW permute.  State-dict keys and shapes are the reference's (`conv1.*`, `bn.*` with the three running
+buffers, `conv2.*`), so a checkpoint's `local_mp.*` entries load unchanged.  The batch statistics are per process, which is
+what `SyncBatchNorm` does in a single process; exchanging them across ranks is not built.
+
+The rest of XCiT (ConvPatchEmbed, the Fourier positional encoding, XCiT's class-attention blocks, an engine) is not built.
+
+Stand-alone modules in the manner of `ClassifierHead`: the parameters live in a `ParamPack` (the fused optimizers
+update them), forward and backward run through one `torch.autograd.Function` each.  XCA: `ops.gemm`, `ops.xca_fwd` /
+`ops.xca_bwd` and `ops.colsum`.  compute_dtype "bf16": bf16 activations between the stages, GEMMs on the pack's bf16 weight
+shadows; "fp32": everything in fp32.  LPI: bf16 or fp32 activations, every parameter and parameter gradient in fp32.  CPU
+tensors raise: there is no fallback.
 """
 from __future__ import annotations
 
@@ -119,3 +127,104 @@ class XCA(nn.Module):
         dx = torch.empty((B * N, C), dtype=torch.float32, device=dy.device)
         ops.gemm(dqkv, pk.w(self.qkv.weight), dx, b_kmajor=False)
         return dx.view(B, N, C)
+
+
+class _LpiFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mod, x, H, W, *params):
+        ctx.mod = mod
+        ctx.need_dx = x.requires_grad
+        return mod._forward(x, H, W, save=True)
+
+    @staticmethod
+    def backward(ctx, dout):
+        mod = ctx.mod
+        held = mod._pack.begin_backward()       # torch's accumulation contract (packing.ParamPack.begin_backward)
+        dx = mod._backward(dout, ctx.need_dx)
+        mod._pack.end_backward(held)
+        return (None, dx, None, None, *param_grads(mod._pack))
+
+
+class LPI(nn.Module):
+    """Local patch interaction, `forward(x, H, W)` with x [B, H*W, C].  `.train()` / `.eval()` select batch or running
+    statistics; in training the running buffers are updated on the device by the forward (graph-capturable).  The
+    statistics are those of this process: cross-rank exchange (the reference's SyncBatchNorm under DDP) is not built.
+    `conv1`, `bn`, `conv2` only hold the parameters and buffers under the reference's names; they are never called."""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0., kernel_size=3,
+                 compute_dtype="bf16"):
+        super().__init__()
+        out_features = out_features or in_features
+        if out_features != in_features:
+            raise VitmiError(f"LPI: out_features {out_features} != in_features {in_features} (depthwise: they must be equal)")
+        if kernel_size != 3:
+            raise VitmiError(f"LPI: kernel_size {kernel_size} is not built (the reference uses 3)")
+        if act_layer is not nn.GELU:
+            raise VitmiError("LPI: only nn.GELU (erf form) is built as the activation")
+        if drop != 0.:
+            raise VitmiError("LPI: dropout is not built (the reference's LPI ignores drop)")
+        if compute_dtype not in ("bf16", "fp32"):
+            raise VitmiError(f"LPI: compute_dtype must be 'bf16' or 'fp32', got {compute_dtype!r}")
+        if in_features < 8 or in_features % 8:
+            raise VitmiError(f"LPI: C = {in_features} must be a multiple of 8")
+        self.dim, self.compute_dtype = in_features, compute_dtype
+        self.conv1 = nn.Conv2d(in_features, out_features, kernel_size=3, padding=1, groups=out_features)
+        self.act = act_layer()
+        self.bn = nn.BatchNorm2d(in_features)
+        self.conv2 = nn.Conv2d(in_features, out_features, kernel_size=3, padding=1, groups=out_features)
+        self._pack = None
+        self._saved = None
+
+    def engine(self):
+        """(Re)build the flat parameter buffers (after .to(device) / load_state_dict)."""
+        dev = self.bn.weight.device
+        if dev.type != "cuda":
+            raise VitmiError("move the module to the GPU before the first forward")
+        if self._pack is None or not self._pack.is_current() or len(self._pack.params) != sum(1 for _ in self.parameters()):
+            self._pack = ParamPack(list(self.named_parameters()), dev, shadow=False)
+        return self
+
+    @property
+    def pack(self):
+        return self.engine()._pack
+
+    def forward(self, x, H, W):
+        if not x.is_cuda:
+            raise VitmiError("vit_torch_amd.LPI runs on an MI355X (HIP) device; got a CPU tensor and there is no CPU fallback")
+        if x.dim() != 3 or x.shape[-1] != self.dim:
+            raise VitmiError(f"LPI: input must be [B, H*W, {self.dim}], got {tuple(x.shape)}")
+        if x.shape[1] != H * W:
+            raise VitmiError(f"LPI: {x.shape[1]} tokens are not an H x W = {H} x {W} grid")
+        self.engine()
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._pack.params)):
+            return _LpiFn.apply(self, x, H, W, *self._pack.params)
+        return self._forward(x, H, W, save=False)
+
+    # ---- kernels
+    def _forward(self, x, H, W, save):
+        B, N, C = x.shape
+        pk, bn = self._pack, self.bn
+        dt = torch.bfloat16 if self.compute_dtype == "bf16" else torch.float32
+        xa = x.to(dt).contiguous()
+        u = torch.empty_like(xa)
+        out = torch.empty_like(xa)
+        stat = torch.empty((2, C), dtype=torch.float32, device=x.device)
+        ops.lpi_fwd(xa, pk.f32(self.conv1.weight), pk.f32(self.conv1.bias), pk.f32(bn.weight), pk.f32(bn.bias),
+                    pk.f32(self.conv2.weight), pk.f32(self.conv2.bias), bn.running_mean, bn.running_var,
+                    bn.num_batches_tracked, u, stat, out, B, H, W, C, training=self.training,
+                    momentum=bn.momentum, eps=bn.eps)
+        if save:
+            self._saved = (xa, u, stat, self.training, (B, H, W), x.dtype)
+        return out.to(x.dtype)
+
+    def _backward(self, dout, need_dx):
+        if self._saved is None:
+            raise VitmiError("backward called without a saved forward (or called twice)")
+        (xa, u, stat, training, (B, H, W), xdt), self._saved = self._saved, None
+        C, pk, bn = self.dim, self._pack, self.bn
+        dy = dout.to(xa.dtype).contiguous()
+        dx = torch.empty_like(xa)
+        ops.lpi_bwd(xa, u, dy, stat, pk.f32(self.conv1.weight), pk.f32(self.conv1.bias), pk.f32(bn.weight), pk.f32(bn.bias),
+                    pk.f32(self.conv2.weight), dx, pk.g(self.conv1.weight), pk.g(self.conv1.bias), pk.g(bn.weight),
+                    pk.g(bn.bias), pk.g(self.conv2.weight), pk.g(self.conv2.bias), B, H, W, C, training=training)
+        return dx.to(xdt) if need_dx else None
