@@ -1,10 +1,13 @@
 """Engine core shared by VitEngine (vit.py), CaitEngine (cait.py) and SwinEngine (swin.py).
 
 Each engine orders the kernel launches of its model and writes the backward pass by hand; what is the same around that
-order lives here: the GEMM launch wrapper (`engine_gemm`: bf16x3 mode, row padding, profiling, reducer launch flags),
-the `Engine` base class (construction, parameter pack, gradient bookkeeping), the MLP half-block of a transformer block
-(`mlp_forward` / `mlp_backward`), the autograd bridge (`_EngineFn`) and the `EngineModel` mixin that gives the model
-classes their `engine()` / `forward()`.
+order lives here: the GEMM launch wrapper (`engine_gemm`: bf16x3 mode, row padding, reducer launch flags) over the one
+flag lookup (`reducer_flags`) and the one event bracket (`profiled_launch`), the `Engine` base class (construction,
+parameter pack, gradient bookkeeping), the MLP half-block of a transformer block (`mlp_forward` / `mlp_backward`), the
+autograd bridge (`_EngineFn`) and the `EngineModel` mixin that gives the model classes their `engine()` / `forward()`.
+
+The modules that run without an engine (head.ClassifierHead, xcit.XCA, xcit.LPI) share the `PackedModule` mixin and its
+one autograd bridge (`_PackedFn`) at the end of this file.
 """
 from __future__ import annotations
 
@@ -40,11 +43,6 @@ def _head_layers(head) -> Optional[List[tuple]]:
     return None
 
 
-def _timing_events():
-    """Two timing events for one launch of the instrumented (eager) step."""
-    return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-
 def _rows_padded(*tensors) -> bool:
     """True when every given [M, .] tensor's storage reaches ceil256(M) rows at its row stride."""
     for t in tensors:
@@ -57,16 +55,48 @@ def _rows_padded(*tensors) -> bool:
     return True
 
 
+def reducer_flags(eng, passed=None) -> int:
+    """The `launch_flags` of one launch: what the caller passed, else the reducer's (gradient buckets in flight: share
+    the device with RCCL's kernels), else 0.  GradReducer.launch_flags() spends a credit, so it is asked only for a
+    launch that will carry its answer."""
+    if passed is not None:
+        return passed
+    return eng.reducer.launch_flags() if eng.reducer is not None else 0
+
+
+def profiled_launch(eng, name, shape, flops, launch):
+    """Run launch(); when eng.profile is a list, bracket it by two HIP events on the launch stream and append
+    (name, shape, flops, start_event, end_event) (bench.py's roofline leg)."""
+    if eng.profile is None:
+        return launch()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = launch()
+    e1.record()
+    eng.profile.append((name, shape, flops, e0, e1))
+    return out
+
+
+def _profiled_gemm(eng, fn, prefix, A, B, C, k):
+    """fn(A, B, C, **k) (ops.gemm / ops.gemm_split3) as a profiled launch of the algorithmic 2 M N K FLOPs."""
+    if eng.profile is None:                 # the timed step: the launch is not even described
+        return fn(A, B, C, **k)
+    akm, bkm = k.get("a_kmajor", True), k.get("b_kmajor", True)
+    Kdim = A.shape[1] if akm else A.shape[0]
+    return profiled_launch(eng, prefix + ("n" if akm else "t") + ("t" if bkm else "n"), (C.shape[0], C.shape[1], Kdim),
+                           2.0 * C.shape[0] * C.shape[1] * Kdim, lambda: fn(A, B, C, **k))
+
+
 def _engine_gemm_split3(eng, A, B, C, **k):
     """engine_gemm in the "bf16x3" mode: fp32 operands -> three-part bf16 images -> ONE bf16 product over 3K on the tile
     kernels, fp32 epilogue (ops.gemm_split3).  Profiled launches count the algorithmic 2 M N K FLOPs (the mode's own
     roofline is a third of the bf16 peak)."""
-    if eng.reducer is not None:
-        k.setdefault("launch_flags", eng.reducer.launch_flags())
+    k["launch_flags"] = reducer_flags(eng, k.get("launch_flags"))
     if k.get("C2") is not None and k.get("epilogue") == EPI_RESIDUAL:
         # CaiT's LayerScale residual x + gamma * f(x) with the branch output f kept for d gamma (models/cait.py:143-150): the
         # tile kernel writes that second output in the OPERAND dtype (bf16 here), so the mode takes three steps, each the
-        # reference's own rounding: f = A W^T + b (three-product GEMM, fp32), out = gamma * f, out += x
+        # reference's own rounding: f = A W^T + b (three-product GEMM, fp32; it carries the flags taken above), out = gamma * f,
+        # out += x
         if k.get("rowscale") is not None or not (C.is_contiguous() and k["R"].is_contiguous()):
             raise VitmiError("compute_dtype='bf16x3': LayerScale residual with a DropPath row scale / strided rows is not built")
         f, R_, gamma = k.pop("C2"), k.pop("R"), k.pop("gamma", None)
@@ -75,22 +105,12 @@ def _engine_gemm_split3(eng, A, B, C, **k):
         ops.scale_cast(f, C, gamma, M=C.shape[0], N=C.shape[1])
         ops.axpy(R_.reshape(-1), C.reshape(-1), 1.0)
         return C
-    if eng.profile is None:
-        return ops.gemm_split3(A, B, C, **k)
-    akm, bkm = k.get("a_kmajor", True), k.get("b_kmajor", True)
-    Kdim = A.shape[1] if akm else A.shape[0]
-    e0, e1 = _timing_events()
-    e0.record()
-    ops.gemm_split3(A, B, C, **k)
-    e1.record()
-    name = "gemm3_" + ("n" if akm else "t") + ("t" if bkm else "n")
-    eng.profile.append((name, (C.shape[0], C.shape[1], Kdim), 2.0 * C.shape[0] * C.shape[1] * Kdim, e0, e1))
-    return C
+    return _profiled_gemm(eng, ops.gemm_split3, "gemm3_", A, B, C, k)
 
 
 def engine_gemm(eng, A, B, C, **k):
-    """ops.gemm for an engine; when eng.profile is a list, each launch is bracketed by HIP events on the launch stream
-    (bench.py's roofline leg)."""
+    """ops.gemm for an engine: the bf16x3 mode, the GELU epilogues' derivative form, the reducer's launch flags, the
+    row-padding flag, and profiling (profiled_launch)."""
     # the block MLPs keep gelu'(pre) instead of pre in bf16 mode: the GELU epilogue has the exp
     # at hand, and the backward epilogue becomes a multiply (vitmi_gemm_desc.aux_is_derivative).
     # fp32 (parity) mode keeps the pre-activation, as the reference's autograd does.
@@ -98,24 +118,13 @@ def engine_gemm(eng, A, B, C, **k):
         return _engine_gemm_split3(eng, A, B, C, **k)
     if k.get("epilogue") in (EPI_BIAS_GELU, EPI_DGELU):
         k.setdefault("aux_deriv", eng.T == torch.bfloat16)
-    if eng.reducer is not None:             # gradient buckets in flight: share the device with RCCL's kernels
-        k.setdefault("launch_flags", eng.reducer.launch_flags())
+    k["launch_flags"] = reducer_flags(eng, k.get("launch_flags"))
     if eng.pad_rows and _rows_padded(C, k.get("C2"), k.get("R"), k.get("aux")):
         # every [M, .] activation of this engine comes from _alloc (rows rounded up to 256); the flag is only passed when the
         # storage behind each row-indexed output / side input really covers the padding (a future torch.empty
         # output would otherwise be a silent out-of-bounds write of up to 255 rows)
-        k["launch_flags"] = k.get("launch_flags", 0) | LAUNCH_ROWS_PADDED
-    if eng.profile is None:
-        return ops.gemm(A, B, C, **k)
-    akm, bkm = k.get("a_kmajor", True), k.get("b_kmajor", True)
-    Kdim = A.shape[1] if akm else A.shape[0]
-    e0, e1 = _timing_events()
-    e0.record()
-    ops.gemm(A, B, C, **k)
-    e1.record()
-    name = "gemm_" + ("n" if akm else "t") + ("t" if bkm else "n")
-    eng.profile.append((name, (C.shape[0], C.shape[1], Kdim), 2.0 * C.shape[0] * C.shape[1] * Kdim, e0, e1))
-    return C
+        k["launch_flags"] |= LAUNCH_ROWS_PADDED
+    return _profiled_gemm(eng, ops.gemm, "gemm_", A, B, C, k)
 
 
 def engine_wgrad_pair(eng, dY0, X0, dW0, dY1, X1, dW1):
@@ -127,17 +136,13 @@ def engine_wgrad_pair(eng, dY0, X0, dW0, dY1, X1, dW1):
         eng._gemm(dY0, X0, dW0, a_kmajor=False, b_kmajor=False)
         eng._gemm(dY1, X1, dW1, a_kmajor=False, b_kmajor=False)
         return
-    flags = eng.reducer.launch_flags() if eng.reducer is not None else 0
-    if eng.profile is None:
-        ops.gemm_pair(dY0, X0, dW0, dY1, X1, dW1, launch_flags=flags)
-        return
-    e0, e1 = _timing_events()
-    e0.record()
-    ops.gemm_pair(dY0, X0, dW0, dY1, X1, dW1, launch_flags=flags)
-    e1.record()
+    flags = reducer_flags(eng)
+    if eng.profile is None:                 # as in _profiled_gemm
+        return ops.gemm_pair(dY0, X0, dW0, dY1, X1, dW1, launch_flags=flags)
     K = dY0.shape[0]
-    flops = 2.0 * K * (dW0.shape[0] * dW0.shape[1] + dW1.shape[0] * dW1.shape[1])
-    eng.profile.append(("gemm_tn_pair", (dW0.shape[0] + dW1.shape[0], dW0.shape[1], K), flops, e0, e1))
+    profiled_launch(eng, "gemm_tn_pair", (dW0.shape[0] + dW1.shape[0], dW0.shape[1], K),
+                    2.0 * K * (dW0.shape[0] * dW0.shape[1] + dW1.shape[0] * dW1.shape[1]),
+                    lambda: ops.gemm_pair(dY0, X0, dW0, dY1, X1, dW1, launch_flags=flags))
 
 
 # ------------------------------------------------------------ MLP half-block --
@@ -199,7 +204,7 @@ class Engine:
         self.pack = ParamPack(list(model.named_parameters()), dev, shadow=self.T == torch.bfloat16)
         self.saved = None
         self.reducer = None          # ddp.GradReducer: told when a section's grads are final
-        self.profile = None          # list of (name, flops, start_event, end_event) when profiling
+        self.profile = None          # list of (name, shape, flops, start_event, end_event) when profiling (profiled_launch)
         # (round 1 ran the weight-gradient GEMMs on a second HIP stream; A/B on one box,
         # profiles/r02_ab_overlap*: 38.47-38.67 ms/step without it, 38.55-39.26 with it — a
         # 256x256-tile GEMM workgroup owns its CU's whole register file and 128 KiB of LDS, so
@@ -254,12 +259,16 @@ class Engine:
             raise
 
     def _take_saved(self):
-        """The saved forward, handed out once."""
-        s = self.saved
-        if s is None:
-            raise VitmiError("backward called without a saved forward (or called twice)")
-        self.saved = None
-        return s
+        return take_saved(self, "saved")
+
+
+def take_saved(owner, attr):
+    """The saved forward kept in owner.<attr>, handed out once."""
+    s = getattr(owner, attr)
+    if s is None:
+        raise VitmiError("backward called without a saved forward (or called twice)")
+    setattr(owner, attr, None)
+    return s
 
 
 def param_grads(pack):
@@ -308,3 +317,63 @@ class EngineModel:
         if torch.is_grad_enabled() and any(p.requires_grad for p in eng.pack.params):
             return _EngineFn.apply(eng, x, *eng.pack.params)
         return eng.forward(x, save=False)
+
+
+# ------------------------------------------------------- stand-alone modules --
+class _PackedFn(torch.autograd.Function):
+    """The autograd bridge of every PackedModule; `extra`: the forward's non-tensor arguments as a plain tuple."""
+
+    @staticmethod
+    def forward(ctx, mod, x, extra, *params):
+        ctx.mod = mod
+        ctx.need_dx = x.requires_grad
+        return mod._forward(x, *extra, save=True)
+
+    @staticmethod
+    def backward(ctx, dout):
+        mod = ctx.mod
+        held = mod._pack.begin_backward()       # torch's accumulation contract (packing.ParamPack.begin_backward)
+        dx = mod._backward(dout, ctx.need_dx)
+        mod._pack.end_backward(held)
+        return (None, dx, None, *param_grads(mod._pack))
+
+
+class PackedModule:
+    """Mixin of an nn.Module that runs on libvitmi kernels by itself (ClassifierHead, XCA, LPI), not inside a model's
+    Engine: its parameters live in a ParamPack (the fused optimizers update them) and one autograd.Function carries
+    its forward and backward.  It holds plain attributes only: nothing enters a state_dict, and parameter names, order
+    and pack layout are the module's own.  A subclass lists it BEFORE its nn.Module base, sets `pack_shadow` where its
+    GEMMs read the pack's bf16 weight shadows, checks its input in `forward` (`_refuse_cpu`, its shapes) and ends it with
+    `self._run(x, *extra)`, and writes `_forward(x, *extra, save)`, which keeps what the backward needs in
+    `self._saved` when `save`, and `_backward(dout, need_dx)`, which starts from `self._take_saved()`, writes the
+    parameter gradients into the pack (`self._pack.g(p)`) and returns dL/dx (None when not need_dx)."""
+    _pack = None
+    _saved = None
+    pack_shadow = False
+
+    def engine(self):
+        """(Re)build the flat parameter buffers (after .to(device) / load_state_dict)."""
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise VitmiError(f"move the {type(self).__name__} to the GPU before the first forward")
+        if self._pack is None or not self._pack.is_current() or len(self._pack.params) != sum(1 for _ in self.parameters()):
+            self._pack = ParamPack(list(self.named_parameters()), dev, shadow=self.pack_shadow)
+        return self
+
+    @property
+    def pack(self):
+        return self.engine()._pack
+
+    def _refuse_cpu(self, x):
+        if not x.is_cuda:
+            raise VitmiError(f"vit_torch_amd.{type(self).__name__} runs on an MI355X (HIP) device; got a CPU tensor "
+                             "and there is no CPU fallback")
+
+    def _run(self, x, *extra):
+        self.engine()
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._pack.params)):
+            return _PackedFn.apply(self, x, extra, *self._pack.params)
+        return self._forward(x, *extra, save=False)
+
+    def _take_saved(self):
+        return take_saved(self, "_saved")

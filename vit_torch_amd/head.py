@@ -7,7 +7,9 @@ model, the model's engine runs it; in the reference's linear-evaluation mode
 (`utils_network.py:143,202-206,413-415`).  `ClassifierHead` is that module: the same
 `nn.Sequential` structure and state-dict keys ("0.weight", "0.bias", "2.weight", ...), but
 `forward` / `backward` run the fp32 MFMA GEMM with fused bias+GELU / gelu' epilogues, and its
-parameters live in a `ParamPack`, so `FusedSGD` updates them.  CPU tensors raise: no fallback.
+parameters live in a `ParamPack`, so `FusedSGD` updates them.  CPU tensors raise: no fallback.  The pack, the autograd
+bridge and the dispatch are `engine.PackedModule`'s; here are the head's kernels, its reducer hand-off and the early
+return of an empty head.
 """
 from __future__ import annotations
 
@@ -16,8 +18,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import EPI_BIAS_GELU, EPI_DGELU, VitmiError
-from .engine import _head_layers, param_grads
-from .packing import ParamPack
+from .engine import PackedModule, _head_layers
 
 
 def head_forward(pack, layers, x):
@@ -63,56 +64,19 @@ def head_backward(pack, layers, saved, d, need_dx=True):
     return d
 
 
-class _HeadFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, head, x, *params):
-        ctx.head = head
-        ctx.need_dx = x.requires_grad
-        return head._forward(x, save=True)
-
-    @staticmethod
-    def backward(ctx, dout):
-        head = ctx.head
-        held = head._pack.begin_backward()      # torch's accumulation contract (packing.ParamPack.begin_backward)
-        dx = head._backward(dout, ctx.need_dx)
-        head._pack.end_backward(held)
-        return (None, dx, *param_grads(head._pack))
-
-
-class ClassifierHead(nn.Sequential):
+class ClassifierHead(PackedModule, nn.Sequential):
     def __init__(self, *layers):
         super().__init__(*layers)
         self._layers = _head_layers(self)
         if self._layers is None:
             raise VitmiError("ClassifierHead: layers must be Linear[, GELU], ..., Linear")
-        self._pack = None
-        self._saved = None
         self.reducer = None          # ddp.GradReducer (Network(ddp=...)): the head's gradients leave as one bucket after its backward
 
-    def engine(self):
-        """(Re)build the flat parameter buffers (after .to(device) / load_state_dict)."""
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise VitmiError("move the head to the GPU before the first forward")
-        if self._pack is None or not self._pack.is_current() or len(self._pack.params) != sum(1 for _ in self.parameters()):
-            self._pack = ParamPack(list(self.named_parameters()), dev, shadow=False)
-        return self
-
-    @property
-    def pack(self):
-        return self.engine()._pack
-
     def forward(self, x):
-        if not x.is_cuda:
-            raise VitmiError("vit_torch_amd heads run on an MI355X (HIP) device; got a CPU tensor "
-                             "and there is no CPU fallback")
+        self._refuse_cpu(x)
         if not self._layers:
             return x
-        self.engine()
-        x = x.float().contiguous()
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._pack.params)):
-            return _HeadFn.apply(self, x, *self._pack.params)
-        return self._forward(x, save=False)
+        return self._run(x.float().contiguous())
 
     # ---- kernels
     def _forward(self, x, save):
@@ -123,10 +87,7 @@ class ClassifierHead(nn.Sequential):
 
     def _backward(self, dout, need_dx):
         try:
-            if self._saved is None:
-                raise VitmiError("backward called without a saved forward (or called twice)")
-            saved, self._saved = self._saved, None
-            dx = head_backward(self._pack, self._layers, saved, dout.contiguous().float(), need_dx)
+            dx = head_backward(self._pack, self._layers, self._take_saved(), dout.contiguous().float(), need_dx)
         except BaseException:
             if self.reducer is not None:
                 self.reducer.abort()

@@ -17,12 +17,18 @@ from ._lib import (BF16, EPI_BIAS_GELU, EPI_DGELU, EPI_PATCH_POS, EPI_RESIDUAL, 
 _WS: dict = {}
 
 
+def dtype_code_or_neg(t) -> int:
+    """The ABI's dtype code (BF16 / F32) of a tensor or a torch.dtype, -1 for a dtype the library does not take: what the
+    host-only `*_supported` queries pass on."""
+    dt = t if isinstance(t, torch.dtype) else t.dtype
+    return BF16 if dt == torch.bfloat16 else F32 if dt == torch.float32 else -1
+
+
 def dtype_code(t: torch.Tensor) -> int:
-    if t.dtype == torch.bfloat16:
-        return BF16
-    if t.dtype == torch.float32:
-        return F32
-    raise TypeError(f"vitmi: unsupported dtype {t.dtype}")
+    code = dtype_code_or_neg(t)
+    if code < 0:
+        raise TypeError(f"vitmi: unsupported dtype {t.dtype}")
+    return code
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -49,15 +55,25 @@ def workspace(nbytes: int, device) -> torch.Tensor:
     return w
 
 
-def gemm(A, B, C_out, *, a_kmajor=True, b_kmajor=True, epilogue=EPI_STORE, bias=None, R=None,
-         gamma=None, aux=None, C2=None, pos=None, n_tok=0, cls=None, alpha=1.0, accumulate=False,
-         impl=GEMM_AUTO, rowscale=None, rows_per_group=0, colsum_part=None, aux_deriv=False,
-         launch_flags=0):
-    """C = epilogue(op(A) @ op(B)^T); see vitmi_gemm in include/vitmi.h."""
-    d = _gemm_desc(A, B, C_out, a_kmajor=a_kmajor, b_kmajor=b_kmajor, epilogue=epilogue, bias=bias, R=R, gamma=gamma,
-                   aux=aux, C2=C2, pos=pos, n_tok=n_tok, cls=cls, alpha=alpha, accumulate=accumulate, impl=impl,
-                   rowscale=rowscale, rows_per_group=rows_per_group, colsum_part=colsum_part, aux_deriv=aux_deriv,
-                   launch_flags=launch_flags)
+def _aligned_ws(need: int, device, none_if_unneeded=False):
+    """`need` bytes of the workspace behind a 256-byte-aligned address: (pointer, bytes from there on); (None, 0) for
+    need == 0 where the kernel family takes "no workspace" that way."""
+    if none_if_unneeded and not need:
+        return None, 0
+    w = workspace(need + 256, device)
+    off = (-w.data_ptr()) % 256
+    return w.data_ptr() + off, w.numel() - off
+
+
+def _contract(who, name, t, dtype, numel, shape):
+    """A tensor argument's contract: contiguous, `dtype`, `numel` elements (`shape`: the expected shape, as text)."""
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() != numel:
+        raise _lib.VitmiError(f"{who}: {name} must be a contiguous {dtype} {shape} tensor (got {t.dtype}, {tuple(t.shape)})")
+
+
+def gemm(A, B, C_out, **k):
+    """C = epilogue(op(A) @ op(B)^T); see vitmi_gemm in include/vitmi.h.  The keywords are _gemm_desc's."""
+    d = _gemm_desc(A, B, C_out, **k)
     lib = load()
     need = lib.vitmi_gemm_workspace(C.byref(d))
     if need:
@@ -145,6 +161,12 @@ def _gemm_desc(A, B, C_out, *, a_kmajor=True, b_kmajor=True, epilogue=EPI_STORE,
                gamma=None, aux=None, C2=None, pos=None, n_tok=0, cls=None, alpha=1.0, accumulate=False,
                impl=GEMM_AUTO, rowscale=None, rows_per_group=0, colsum_part=None, aux_deriv=False,
                launch_flags=0):
+    """The vitmi_gemm_desc of one product (include/vitmi.h describes each field).  a_kmajor / b_kmajor: the operand is
+    [rows, K] (else [K, rows]); epilogue: EPI_*; bias [N], gamma [N] (LayerScale), cls [N], pos [n_tok * N]: fp32 vectors of
+    the epilogues; R: the residual [M, N]; aux: the saved pre-activation (or, with aux_deriv, its gelu') of EPI_DGELU;
+    C2: a second [M, N] output (the pre-activation / gelu' of EPI_BIAS_GELU, the branch output of EPI_RESIDUAL);
+    alpha: scale of the product; accumulate: C += ; impl: GEMM_AUTO / _FAST / _GENERIC; rowscale [>= M / rows_per_group]:
+    DropPath's per-sample scale; colsum_part [ceil(M / 128), N]: per-128-row column sums of C; launch_flags: VITMI_LAUNCH_*."""
     _need_cuda(A, B, C_out)
     assert A.dim() == 2 and B.dim() == 2 and C_out.dim() == 2
     assert A.stride(1) == 1 and B.stride(1) == 1 and C_out.stride(1) == 1
@@ -348,34 +370,14 @@ def attn_probs(qkv, P, B, N, H, hd, scale):
 
 def xca_supported(t, H, N, hd) -> bool:
     """Host-only query: do the cross-covariance attention kernels (xca_fwd / xca_bwd) take this dtype and shape?"""
-    code = (BF16 if t == torch.bfloat16 else F32 if t == torch.float32 else -1) if isinstance(t, torch.dtype) else \
-        (BF16 if t.dtype == torch.bfloat16 else F32 if t.dtype == torch.float32 else -1)
-    return bool(load().vitmi_xca_supported(code, H, N, hd))
+    return bool(load().vitmi_xca_supported(dtype_code_or_neg(t), H, N, hd))
 
 
 def _xca_check(who, qkv, temperature, B, N, H, hd):
     if qkv.dtype not in (torch.bfloat16, torch.float32):
         raise _lib.VitmiError(f"{who}: qkv must be bf16 or fp32, got {qkv.dtype}")
-    if not qkv.is_contiguous() or qkv.numel() != B * N * 3 * H * hd:
-        raise _lib.VitmiError(f"{who}: qkv must be a contiguous [B*N, 3*H*hd] = [{B * N}, {3 * H * hd}] tensor "
-                              f"(got {tuple(qkv.shape)})")
-    if temperature.dtype != torch.float32 or not temperature.is_contiguous() or temperature.numel() != H:
-        raise _lib.VitmiError(f"{who}: temperature must be a contiguous fp32 tensor of H = {H} elements "
-                              f"(got {temperature.dtype}, {tuple(temperature.shape)})")
-
-
-def _xca_like(who, name, t, dtype, numel, shape):
-    if t.dtype != dtype or not t.is_contiguous() or t.numel() != numel:
-        raise _lib.VitmiError(f"{who}: {name} must be a contiguous {dtype} {shape} tensor (got {t.dtype}, {tuple(t.shape)})")
-
-
-def _xca_ws(B, H, N, hd, device):
-    need = load().vitmi_xca_workspace(B, H, N, hd)
-    if not need:
-        return None, 0
-    w = workspace(need + 256, device)
-    off = (-w.data_ptr()) % 256
-    return w.data_ptr() + off, w.numel() - off
+    _contract(who, "qkv", qkv, qkv.dtype, B * N * 3 * H * hd, f"[B*N, 3*H*hd] = [{B * N}, {3 * H * hd}]")
+    _contract(who, "temperature", temperature, torch.float32, H, f"[H] = [{H}]")
 
 
 def xca_fwd(qkv, temperature, out, stat, B, N, H, hd):
@@ -384,9 +386,9 @@ def xca_fwd(qkv, temperature, out, stat, B, N, H, hd):
     xca_bwd needs besides qkv (vitmi_xca_fwd).  hd in {32, 48, 64}."""
     _need_cuda(qkv, temperature, out, stat)
     _xca_check("xca_fwd", qkv, temperature, B, N, H, hd)
-    _xca_like("xca_fwd", "out", out, qkv.dtype, B * N * H * hd, f"[B, N, H*hd] = [{B}, {N}, {H * hd}]")
-    _xca_like("xca_fwd", "stat", stat, torch.float32, B * H * (hd + 2) * hd, f"[B, H, hd+2, hd] = [{B}, {H}, {hd + 2}, {hd}]")
-    ptr, nb = _xca_ws(B, H, N, hd, qkv.device)
+    _contract("xca_fwd", "out", out, qkv.dtype, B * N * H * hd, f"[B, N, H*hd] = [{B}, {N}, {H * hd}]")
+    _contract("xca_fwd", "stat", stat, torch.float32, B * H * (hd + 2) * hd, f"[B, H, hd+2, hd] = [{B}, {H}, {hd + 2}, {hd}]")
+    ptr, nb = _aligned_ws(load().vitmi_xca_workspace(B, H, N, hd), qkv.device, none_if_unneeded=True)
     check(load().vitmi_xca_fwd(qkv.data_ptr(), temperature.data_ptr(), out.data_ptr(), stat.data_ptr(), dtype_code(qkv),
                                B, N, H, hd, ptr, nb, _stream()), "vitmi_xca_fwd")
     return out
@@ -397,45 +399,33 @@ def xca_bwd(qkv, dout, temperature, stat, dqkv, dtemp, B, N, H, hd):
     temperature partial per (image, head); their batch sum is a colsum)."""
     _need_cuda(qkv, dout, temperature, stat, dqkv, dtemp)
     _xca_check("xca_bwd", qkv, temperature, B, N, H, hd)
-    _xca_like("xca_bwd", "dout", dout, qkv.dtype, B * N * H * hd, f"[B, N, H*hd] = [{B}, {N}, {H * hd}]")
-    _xca_like("xca_bwd", "dqkv", dqkv, qkv.dtype, B * N * 3 * H * hd, f"[B*N, 3*H*hd] = [{B * N}, {3 * H * hd}]")
-    _xca_like("xca_bwd", "stat", stat, torch.float32, B * H * (hd + 2) * hd, f"[B, H, hd+2, hd] = [{B}, {H}, {hd + 2}, {hd}]")
-    _xca_like("xca_bwd", "dtemp", dtemp, torch.float32, H, f"[H] = [{H}]")
+    _contract("xca_bwd", "dout", dout, qkv.dtype, B * N * H * hd, f"[B, N, H*hd] = [{B}, {N}, {H * hd}]")
+    _contract("xca_bwd", "dqkv", dqkv, qkv.dtype, B * N * 3 * H * hd, f"[B*N, 3*H*hd] = [{B * N}, {3 * H * hd}]")
+    _contract("xca_bwd", "stat", stat, torch.float32, B * H * (hd + 2) * hd, f"[B, H, hd+2, hd] = [{B}, {H}, {hd + 2}, {hd}]")
+    _contract("xca_bwd", "dtemp", dtemp, torch.float32, H, f"[H] = [{H}]")
     part = torch.empty((B, H), dtype=torch.float32, device=qkv.device)
-    ptr, nb = _xca_ws(B, H, N, hd, qkv.device)
+    ptr, nb = _aligned_ws(load().vitmi_xca_workspace(B, H, N, hd), qkv.device, none_if_unneeded=True)
     check(load().vitmi_xca_bwd(qkv.data_ptr(), dout.data_ptr(), temperature.data_ptr(), stat.data_ptr(), dqkv.data_ptr(),
                                part.data_ptr(), dtype_code(qkv), B, N, H, hd, ptr, nb, _stream()), "vitmi_xca_bwd")
     colsum(part, dtemp, M=B, N=H)
     return dqkv
 
 
-def _lpi_code(t):
-    dt = t if isinstance(t, torch.dtype) else t.dtype
-    return BF16 if dt == torch.bfloat16 else F32 if dt == torch.float32 else -1
-
-
 def lpi_supported(t, B, H, W, C) -> bool:
     """Host-only query: do the local patch interaction kernels (lpi_fwd / lpi_bwd) take this dtype and shape?"""
-    return bool(load().vitmi_lpi_supported(_lpi_code(t), B, H, W, C))
+    return bool(load().vitmi_lpi_supported(dtype_code_or_neg(t), B, H, W, C))
 
 
-def _lpi_act(who, name, t, dtype, B, H, W, C):
-    if t.dtype != dtype or not t.is_contiguous() or t.numel() != B * H * W * C:
-        raise _lib.VitmiError(f"{who}: {name} must be a contiguous {dtype} [B, H*W, C] = [{B}, {H * W}, {C}] tensor "
-                              f"(got {t.dtype}, {tuple(t.shape)})")
-
-
-def _lpi_f32(who, name, t, numel):
-    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
-        raise _lib.VitmiError(f"{who}: {name} must be a contiguous fp32 tensor of {numel} elements "
-                              f"(got {t.dtype}, {tuple(t.shape)})")
-
-
-def _lpi_ws(code, B, H, W, C, device):
-    need = load().vitmi_lpi_workspace(code, B, H, W, C)
-    w = workspace(need + 256, device)
-    off = (-w.data_ptr()) % 256
-    return w.data_ptr() + off, w.numel() - off
+def _lpi_contract(who, x, acts, f32s, B, H, W, C):
+    """lpi_fwd / lpi_bwd: x is bf16 or fp32; `acts` (name, tensor) are [B, H*W, C] in x's dtype; `f32s` (name, tensor,
+    elements) are fp32 (a None tensor is an optional one left out)."""
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.VitmiError(f"{who}: x must be bf16 or fp32, got {x.dtype}")
+    for name, t in acts:
+        _contract(who, name, t, x.dtype, B * H * W * C, f"[B, H*W, C] = [{B}, {H * W}, {C}]")
+    for name, t, n in f32s:
+        if t is not None:
+            _contract(who, name, t, torch.float32, n, f"{n}-element")
 
 
 def lpi_fwd(x, w1, b1, gamma, beta, w2, b2, running_mean, running_var, num_batches_tracked, u, stat, out, B, H, W, C, *,
@@ -446,23 +436,16 @@ def lpi_fwd(x, w1, b1, gamma, beta, w2, b2, running_mean, running_var, num_batch
     three running buffers (fp32 [C], fp32 [C], int64 [1]; each may be None) are updated on the device; otherwise the
     running statistics are used and nothing is touched (vitmi_lpi_fwd)."""
     _need_cuda(x, w1, b1, gamma, beta, w2, b2, running_mean, running_var, num_batches_tracked, u, stat, out)
-    if x.dtype not in (torch.bfloat16, torch.float32):
-        raise _lib.VitmiError(f"lpi_fwd: x must be bf16 or fp32, got {x.dtype}")
-    _lpi_act("lpi_fwd", "x", x, x.dtype, B, H, W, C)
-    _lpi_act("lpi_fwd", "u", u, x.dtype, B, H, W, C)
-    _lpi_act("lpi_fwd", "out", out, x.dtype, B, H, W, C)
-    for name, t, n in (("conv1.weight", w1, 9 * C), ("conv1.bias", b1, C), ("bn.weight", gamma, C), ("bn.bias", beta, C),
-                       ("conv2.weight", w2, 9 * C), ("conv2.bias", b2, C), ("stat", stat, 2 * C)):
-        _lpi_f32("lpi_fwd", name, t, n)
-    for name, t in (("running_mean", running_mean), ("running_var", running_var)):
-        if t is not None:
-            _lpi_f32("lpi_fwd", name, t, C)
+    _lpi_contract("lpi_fwd", x, (("x", x), ("u", u), ("out", out)),
+                  (("conv1.weight", w1, 9 * C), ("conv1.bias", b1, C), ("bn.weight", gamma, C), ("bn.bias", beta, C),
+                   ("conv2.weight", w2, 9 * C), ("conv2.bias", b2, C), ("stat", stat, 2 * C),
+                   ("running_mean", running_mean, C), ("running_var", running_var, C)), B, H, W, C)
     if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1):
         raise _lib.VitmiError("lpi_fwd: num_batches_tracked must be an int64 tensor of one element")
     if not training and (running_mean is None or running_var is None):
         raise _lib.VitmiError("lpi_fwd: eval mode needs running_mean and running_var")
     code = dtype_code(x)
-    ptr, nb = _lpi_ws(code, B, H, W, C, x.device)
+    ptr, nb = _aligned_ws(load().vitmi_lpi_workspace(code, B, H, W, C), x.device)
     check(load().vitmi_lpi_fwd(x.data_ptr(), w1.data_ptr(), b1.data_ptr(), gamma.data_ptr(), beta.data_ptr(), w2.data_ptr(),
                                b2.data_ptr(), _ptr(running_mean), _ptr(running_var), _ptr(num_batches_tracked), u.data_ptr(),
                                stat.data_ptr(), out.data_ptr(), code, int(bool(training)), momentum, eps, B, H, W, C,
@@ -474,16 +457,12 @@ def lpi_bwd(x, u, dout, stat, w1, b1, gamma, beta, w2, dx, dw1, db1, dgamma, dbe
     """Backward of lpi_fwd: dx (compute dtype) and the six fp32 parameter gradients, stored, from dout, the saved u and stat
     and x (vitmi_lpi_bwd); training=False is the eval-mode gradient."""
     _need_cuda(x, u, dout, stat, w1, b1, gamma, beta, w2, dx, dw1, db1, dgamma, dbeta, dw2, db2)
-    if x.dtype not in (torch.bfloat16, torch.float32):
-        raise _lib.VitmiError(f"lpi_bwd: x must be bf16 or fp32, got {x.dtype}")
-    for name, t in (("x", x), ("u", u), ("dout", dout), ("dx", dx)):
-        _lpi_act("lpi_bwd", name, t, x.dtype, B, H, W, C)
-    for name, t, n in (("stat", stat, 2 * C), ("conv1.weight", w1, 9 * C), ("conv1.bias", b1, C), ("bn.weight", gamma, C),
-                       ("bn.bias", beta, C), ("conv2.weight", w2, 9 * C), ("dw1", dw1, 9 * C), ("db1", db1, C),
-                       ("dgamma", dgamma, C), ("dbeta", dbeta, C), ("dw2", dw2, 9 * C), ("db2", db2, C)):
-        _lpi_f32("lpi_bwd", name, t, n)
+    _lpi_contract("lpi_bwd", x, (("x", x), ("u", u), ("dout", dout), ("dx", dx)),
+                  (("stat", stat, 2 * C), ("conv1.weight", w1, 9 * C), ("conv1.bias", b1, C), ("bn.weight", gamma, C),
+                   ("bn.bias", beta, C), ("conv2.weight", w2, 9 * C), ("dw1", dw1, 9 * C), ("db1", db1, C),
+                   ("dgamma", dgamma, C), ("dbeta", dbeta, C), ("dw2", dw2, 9 * C), ("db2", db2, C)), B, H, W, C)
     code = dtype_code(x)
-    ptr, nb = _lpi_ws(code, B, H, W, C, x.device)
+    ptr, nb = _aligned_ws(load().vitmi_lpi_workspace(code, B, H, W, C), x.device)
     check(load().vitmi_lpi_bwd(x.data_ptr(), u.data_ptr(), dout.data_ptr(), stat.data_ptr(), w1.data_ptr(), b1.data_ptr(),
                                gamma.data_ptr(), beta.data_ptr(), w2.data_ptr(), dx.data_ptr(), dw1.data_ptr(), db1.data_ptr(),
                                dgamma.data_ptr(), dbeta.data_ptr(), dw2.data_ptr(), db2.data_ptr(), code, int(bool(training)),
@@ -596,14 +575,21 @@ def sgd_momentum(p, g, buf, shadow, lr, momentum, grad_scale=1.0):
                                     _stream()), "vitmi_sgd_momentum")
 
 
-def image_ingest(src, dst, off_y, off_x, flip, mean, std, pad, fill=128):
-    """src uint8 [B,H,W,C] (NHWC) -> dst fp32 [B,C,S,S]; see vitmi_image_ingest."""
+def _ingest_args(src, dst, off_y, off_x, flip, mean, std):
+    """What the four ingest wrappers ask of their arguments: a contiguous uint8 [B,H,W,C] (NHWC) source, a contiguous
+    destination, and the five optional tensors (crop offsets, flip flags, channel mean / std) contiguous, on the GPU and of
+    their dtype.  Returns the source's shape."""
     _need_cuda(src, dst)
-    assert src.dtype == torch.uint8 and src.is_contiguous() and dst.dtype == torch.float32 and dst.is_contiguous()
-    B, H, W, C = src.shape
-    assert dst.shape[0] == B and dst.shape[1] == C and dst.shape[2] == dst.shape[3]
+    assert src.dtype == torch.uint8 and src.is_contiguous() and dst.is_contiguous()
     for t, dt in ((off_y, torch.int32), (off_x, torch.int32), (flip, torch.uint8), (mean, torch.float32), (std, torch.float32)):
         assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous())
+    return src.shape
+
+
+def image_ingest(src, dst, off_y, off_x, flip, mean, std, pad, fill=128):
+    """src uint8 [B,H,W,C] (NHWC) -> dst fp32 [B,C,S,S]; see vitmi_image_ingest."""
+    B, H, W, C = _ingest_args(src, dst, off_y, off_x, flip, mean, std)
+    assert dst.dtype == torch.float32 and dst.shape[0] == B and dst.shape[1] == C and dst.shape[2] == dst.shape[3]
     check(load().vitmi_image_ingest(src.data_ptr(), dst.data_ptr(), _ptr(off_y), _ptr(off_x), _ptr(flip), _ptr(mean),
                                     _ptr(std), B, H, W, C, dst.shape[2], int(pad), int(fill), _stream()),
           "vitmi_image_ingest")
@@ -612,13 +598,8 @@ def image_ingest(src, dst, off_y, off_x, flip, mean, std, pad, fill=128):
 
 def ingest_patchify(src, out, off_y, off_x, flip, mean, std, S, pad, p, cls_rows, fill=128):
     """src uint8 [B,H,W,C] (NHWC) -> out [B*(cls_rows + (S/p)^2), ld >= C*p*p] patch rows; see vitmi_ingest_patchify."""
-    _need_cuda(src, out)
-    assert src.dtype == torch.uint8 and src.is_contiguous() and out.dim() == 2 and out.is_contiguous()
-    B, H, W, C = src.shape
-    g = S // p
-    assert out.shape[0] == B * (cls_rows + g * g) and out.shape[1] >= C * p * p
-    for t, dt in ((off_y, torch.int32), (off_x, torch.int32), (flip, torch.uint8), (mean, torch.float32), (std, torch.float32)):
-        assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous())
+    B, H, W, C = _ingest_args(src, out, off_y, off_x, flip, mean, std)
+    assert out.dim() == 2 and out.shape[0] == B * (cls_rows + (S // p) ** 2) and out.shape[1] >= C * p * p
     check(load().vitmi_ingest_patchify(src.data_ptr(), out.data_ptr(), dtype_code(out), out.shape[1], _ptr(off_y), _ptr(off_x),
                                        _ptr(flip), _ptr(mean), _ptr(std), B, H, W, C, int(S), int(pad), int(fill), int(p),
                                        int(cls_rows), _stream()), "vitmi_ingest_patchify")
@@ -634,12 +615,8 @@ def _resize_tables(ytab, xtab):
 def resize_ingest(src, dst, ytab, xtab, off_y, off_x, flip, mean, std, pad, fill=128):
     """src uint8 [B,H,W,C] (NHWC) -> Pillow bicubic to ytab.shape[1] x xtab.shape[1] -> crop/flip/normalize -> dst fp32
     [B,C,S,S]; tables from vit_torch_amd.resize.table.  See vitmi_resize_ingest."""
-    _need_cuda(src, dst)
-    assert src.dtype == torch.uint8 and src.is_contiguous() and dst.dtype == torch.float32 and dst.is_contiguous()
-    B, H, W, C = src.shape
-    assert dst.shape[0] == B and dst.shape[1] == C and dst.shape[2] == dst.shape[3]
-    for t, dt in ((off_y, torch.int32), (off_x, torch.int32), (flip, torch.uint8), (mean, torch.float32), (std, torch.float32)):
-        assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous())
+    B, H, W, C = _ingest_args(src, dst, off_y, off_x, flip, mean, std)
+    assert dst.dtype == torch.float32 and dst.shape[0] == B and dst.shape[1] == C and dst.shape[2] == dst.shape[3]
     check(load().vitmi_resize_ingest(src.data_ptr(), dst.data_ptr(), *_resize_tables(ytab, xtab), _ptr(off_y), _ptr(off_x),
                                      _ptr(flip), _ptr(mean), _ptr(std), B, H, W, C, dst.shape[2], int(pad), int(fill),
                                      _stream()), "vitmi_resize_ingest")
@@ -649,13 +626,8 @@ def resize_ingest(src, dst, ytab, xtab, off_y, off_x, flip, mean, std, pad, fill
 def resize_ingest_patchify(src, out, ytab, xtab, off_y, off_x, flip, mean, std, S, pad, p, cls_rows, fill=128):
     """resize_ingest written straight into patch rows [B*(cls_rows + (S/p)^2), ld >= C*p*p]; see
     vitmi_resize_ingest_patchify."""
-    _need_cuda(src, out)
-    assert src.dtype == torch.uint8 and src.is_contiguous() and out.dim() == 2 and out.is_contiguous()
-    B, H, W, C = src.shape
-    g = S // p
-    assert out.shape[0] == B * (cls_rows + g * g) and out.shape[1] >= C * p * p
-    for t, dt in ((off_y, torch.int32), (off_x, torch.int32), (flip, torch.uint8), (mean, torch.float32), (std, torch.float32)):
-        assert t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous())
+    B, H, W, C = _ingest_args(src, out, off_y, off_x, flip, mean, std)
+    assert out.dim() == 2 and out.shape[0] == B * (cls_rows + (S // p) ** 2) and out.shape[1] >= C * p * p
     check(load().vitmi_resize_ingest_patchify(src.data_ptr(), out.data_ptr(), dtype_code(out), out.shape[1],
                                               *_resize_tables(ytab, xtab), _ptr(off_y), _ptr(off_x), _ptr(flip), _ptr(mean),
                                               _ptr(std), B, H, W, C, int(S), int(pad), int(fill), int(p), int(cls_rows),
@@ -797,21 +769,14 @@ def th_long_bwd(qkv, dO, Wl, bl, Ww, bw, dqkv, dWl, dbl, dWw, dbw, B, H, N, hd, 
 
 def th_attn_supported(t, H, N, hd) -> bool:
     """Host-only query: do the fused talking-heads kernels take this shape / dtype?"""
-    code = (BF16 if t == torch.bfloat16 else F32 if t == torch.float32 else -1) if isinstance(t, torch.dtype) else dtype_code(t)
-    return bool(load().vitmi_th_attn_supported(code, H, N, hd))
-
-
-def _th_ws(B, H, N, hd, device):
-    w = workspace(load().vitmi_th_attn_workspace(B, H, N, hd) + 256, device)
-    off = (-w.data_ptr()) % 256
-    return w.data_ptr() + off, w.numel() - off
+    return bool(load().vitmi_th_attn_supported(dtype_code_or_neg(t), H, N, hd))
 
 
 def th_attn_fwd(qkv, Wl, bl, Ww, bw, out, B, H, N, hd, scale):
     """out [B,N,H,hd] = talking-heads attention of qkv [B,N,3,H,hd] (vitmi_th_attn_fwd: scores never leave the CU)."""
     _need_cuda(qkv, out)
     assert qkv.is_contiguous() and out.is_contiguous()
-    ptr, nb = _th_ws(B, H, N, hd, qkv.device)
+    ptr, nb = _aligned_ws(load().vitmi_th_attn_workspace(B, H, N, hd), qkv.device)
     check(load().vitmi_th_attn_fwd(qkv.data_ptr(), Wl.data_ptr(), bl.data_ptr(), Ww.data_ptr(), bw.data_ptr(), out.data_ptr(),
                                    dtype_code(qkv), B, H, N, hd, float(scale), ptr, nb, _stream()), "vitmi_th_attn_fwd")
     return out
@@ -821,7 +786,7 @@ def th_attn_bwd(qkv, dout, Wl, bl, Ww, bw, dqkv, dS, Pm, ld, dWl, dbl, dWw, dbw,
     """dQ into dqkv's q slots, dS and Pm ([B,H,N,ld]) for the caller's dK / dV products, the four mixing-parameter gradients."""
     _need_cuda(qkv, dout, dqkv, dS, Pm)
     assert qkv.is_contiguous() and dout.is_contiguous() and dqkv.is_contiguous() and dS.is_contiguous() and Pm.is_contiguous()
-    ptr, nb = _th_ws(B, H, N, hd, qkv.device)
+    ptr, nb = _aligned_ws(load().vitmi_th_attn_workspace(B, H, N, hd), qkv.device)
     check(load().vitmi_th_attn_bwd(qkv.data_ptr(), dout.data_ptr(), Wl.data_ptr(), bl.data_ptr(), Ww.data_ptr(), bw.data_ptr(),
                                    dqkv.data_ptr(), dS.data_ptr(), Pm.data_ptr(), ld, dWl.data_ptr(), dbl.data_ptr(), dWw.data_ptr(),
                                    dbw.data_ptr(), dtype_code(qkv), B, H, N, hd, float(scale), ptr, nb, _stream()), "vitmi_th_attn_bwd")

@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import EPI_BIAS_GELU, EPI_DGELU, EPI_PATCH_POS, EPI_RESIDUAL, VitmiError
-from .engine import Engine, EngineModel, engine_wgrad_pair, mlp_backward, mlp_forward
+from .engine import Engine, EngineModel, engine_wgrad_pair, mlp_backward, mlp_forward, reducer_flags
 from .head import head_backward, head_forward
 from .posembed import tables_for
 from .data import PatchRows
@@ -499,8 +499,7 @@ class VitEngine(Engine):
             dqkv_part = None
             if T == torch.bfloat16 and a.qkv.bias is not None:
                 dqkv_part = torch.empty((ops.attn_bwd_dbias_rows(B, N), 3 * D), dtype=torch.float32, device=dev)
-            ops.attn_bwd(qkv, O, dO, lse, dqkv, B, N, H, hd, a.scale, dbias_part=dqkv_part,
-                         launch_flags=self.reducer.launch_flags() if self.reducer is not None else 0)
+            ops.attn_bwd(qkv, O, dO, lse, dqkv, B, N, H, hd, a.scale, dbias_part=dqkv_part, launch_flags=reducer_flags(self))
             # the proj and qkv weight gradients share one split-K launch (Gb still holds this block's G' here: the
             # LayerNorm backward below is what overwrites it)
             engine_wgrad_pair(self, Gb, O, pk.g(a.proj.weight), dqkv, ln1, pk.g(a.qkv.weight))

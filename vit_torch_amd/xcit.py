@@ -13,8 +13,9 @@ what `SyncBatchNorm` does in a single process; exchanging them across ranks is n
 
 The rest of XCiT (ConvPatchEmbed, the Fourier positional encoding, XCiT's class-attention blocks, an engine) is not built.
 
-Stand-alone modules in the manner of `ClassifierHead`: the parameters live in a `ParamPack` (the fused optimizers
-update them), forward and backward run through one `torch.autograd.Function` each.  XCA: `ops.gemm`, `ops.xca_fwd` /
+Stand-alone modules on `engine.PackedModule`, as `ClassifierHead` is: the parameters live in a `ParamPack` (the fused
+optimizers update them), forward and backward run through the mixin's one `torch.autograd.Function`; each class here
+keeps its constructor, its input checks and its `_forward` / `_backward`.  XCA: `ops.gemm`, `ops.xca_fwd` /
 `ops.xca_bwd` and `ops.colsum`.  compute_dtype "bf16": bf16 activations between the stages, GEMMs on the pack's bf16 weight
 shadows; "fp32": everything in fp32.  LPI: bf16 or fp32 activations, every parameter and parameter gradient in fp32.  CPU
 tensors raise: there is no fallback.
@@ -26,27 +27,10 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import VitmiError
-from .engine import param_grads
-from .packing import ParamPack
+from .engine import PackedModule
 
 
-class _XcaFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mod, x, *params):
-        ctx.mod = mod
-        ctx.need_dx = x.requires_grad
-        return mod._forward(x, save=True)
-
-    @staticmethod
-    def backward(ctx, dout):
-        mod = ctx.mod
-        held = mod._pack.begin_backward()       # torch's accumulation contract (packing.ParamPack.begin_backward)
-        dx = mod._backward(dout, ctx.need_dx)
-        mod._pack.end_backward(held)
-        return (None, dx, *param_grads(mod._pack))
-
-
-class XCA(nn.Module):
+class XCA(PackedModule, nn.Module):
     def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_drop=0., proj_drop=0., compute_dtype="bf16"):
         super().__init__()
         if attn_drop != 0. or proj_drop != 0.:
@@ -59,34 +43,16 @@ class XCA(nn.Module):
         self.temperature = nn.Parameter(torch.ones(num_heads, 1, 1))
         self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
         self.proj = nn.Linear(dim, dim)
-        self._pack = None
-        self._saved = None
+        self.pack_shadow = compute_dtype == "bf16"        # the GEMMs read the bf16 weight shadows
 
     def no_weight_decay(self):
         return {"temperature"}
 
-    def engine(self):
-        """(Re)build the flat parameter buffers (after .to(device) / load_state_dict)."""
-        dev = self.temperature.device
-        if dev.type != "cuda":
-            raise VitmiError("move the module to the GPU before the first forward")
-        if self._pack is None or not self._pack.is_current() or len(self._pack.params) != sum(1 for _ in self.parameters()):
-            self._pack = ParamPack(list(self.named_parameters()), dev, shadow=self.compute_dtype == "bf16")
-        return self
-
-    @property
-    def pack(self):
-        return self.engine()._pack
-
     def forward(self, x):
-        if not x.is_cuda:
-            raise VitmiError("vit_torch_amd.XCA runs on an MI355X (HIP) device; got a CPU tensor and there is no CPU fallback")
+        self._refuse_cpu(x)
         if x.dim() != 3 or x.shape[-1] != self.dim:
             raise VitmiError(f"XCA: input must be [B, N, {self.dim}], got {tuple(x.shape)}")
-        self.engine()
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._pack.params)):
-            return _XcaFn.apply(self, x, *self._pack.params)
-        return self._forward(x, save=False)
+        return self._run(x)
 
     # ---- kernels
     def _forward(self, x, save):
@@ -107,9 +73,7 @@ class XCA(nn.Module):
         return y.view(B, N, C)
 
     def _backward(self, dout, need_dx):
-        if self._saved is None:
-            raise VitmiError("backward called without a saved forward (or called twice)")
-        (xa, qkv, att, stat, (B, N)), self._saved = self._saved, None
+        xa, qkv, att, stat, (B, N) = self._take_saved()
         C, H, pk = self.dim, self.num_heads, self._pack
         hd, dt = C // H, xa.dtype
         dy = dout.reshape(B * N, C).to(dt).contiguous()
@@ -129,23 +93,7 @@ class XCA(nn.Module):
         return dx.view(B, N, C)
 
 
-class _LpiFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mod, x, H, W, *params):
-        ctx.mod = mod
-        ctx.need_dx = x.requires_grad
-        return mod._forward(x, H, W, save=True)
-
-    @staticmethod
-    def backward(ctx, dout):
-        mod = ctx.mod
-        held = mod._pack.begin_backward()       # torch's accumulation contract (packing.ParamPack.begin_backward)
-        dx = mod._backward(dout, ctx.need_dx)
-        mod._pack.end_backward(held)
-        return (None, dx, None, None, *param_grads(mod._pack))
-
-
-class LPI(nn.Module):
+class LPI(PackedModule, nn.Module):
     """Local patch interaction, `forward(x, H, W)` with x [B, H*W, C].  `.train()` / `.eval()` select batch or running
     statistics; in training the running buffers are updated on the device by the forward (graph-capturable).  The
     statistics are those of this process: cross-rank exchange (the reference's SyncBatchNorm under DDP) is not built.
@@ -172,33 +120,14 @@ class LPI(nn.Module):
         self.act = act_layer()
         self.bn = nn.BatchNorm2d(in_features)
         self.conv2 = nn.Conv2d(in_features, out_features, kernel_size=3, padding=1, groups=out_features)
-        self._pack = None
-        self._saved = None
-
-    def engine(self):
-        """(Re)build the flat parameter buffers (after .to(device) / load_state_dict)."""
-        dev = self.bn.weight.device
-        if dev.type != "cuda":
-            raise VitmiError("move the module to the GPU before the first forward")
-        if self._pack is None or not self._pack.is_current() or len(self._pack.params) != sum(1 for _ in self.parameters()):
-            self._pack = ParamPack(list(self.named_parameters()), dev, shadow=False)
-        return self
-
-    @property
-    def pack(self):
-        return self.engine()._pack
 
     def forward(self, x, H, W):
-        if not x.is_cuda:
-            raise VitmiError("vit_torch_amd.LPI runs on an MI355X (HIP) device; got a CPU tensor and there is no CPU fallback")
+        self._refuse_cpu(x)
         if x.dim() != 3 or x.shape[-1] != self.dim:
             raise VitmiError(f"LPI: input must be [B, H*W, {self.dim}], got {tuple(x.shape)}")
         if x.shape[1] != H * W:
             raise VitmiError(f"LPI: {x.shape[1]} tokens are not an H x W = {H} x {W} grid")
-        self.engine()
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._pack.params)):
-            return _LpiFn.apply(self, x, H, W, *self._pack.params)
-        return self._forward(x, H, W, save=False)
+        return self._run(x, H, W)
 
     # ---- kernels
     def _forward(self, x, H, W, save):
@@ -218,9 +147,7 @@ class LPI(nn.Module):
         return out.to(x.dtype)
 
     def _backward(self, dout, need_dx):
-        if self._saved is None:
-            raise VitmiError("backward called without a saved forward (or called twice)")
-        (xa, u, stat, training, (B, H, W), xdt), self._saved = self._saved, None
+        xa, u, stat, training, (B, H, W), xdt = self._take_saved()
         C, pk, bn = self.dim, self._pack, self.bn
         dy = dout.to(xa.dtype).contiguous()
         dx = torch.empty_like(xa)
