@@ -536,7 +536,8 @@ extern "C" int vitmi_layernorm_bwd_deferred(const void* dy, int dy_dtype, int64_
   VITMI_REQUIRE(dy_stride % 4 == 0 && g_stride % 4 == 0 && (!gb_out || gb_stride % 4 == 0), VITMI_E_ALIGN, "layernorm_bwd: strides must be multiples of 4");
   VITMI_REQUIRE(is_aligned(dy, 4 * dtype_size(dy_dtype)) && is_aligned(g_out, 4 * dtype_size(g_dtype)) &&
                     (!g_in || is_aligned(g_in, 4 * dtype_size(g_dtype))) &&
-                    (!gb_out || is_aligned(gb_out, 4 * dtype_size(gb_dtype))) && is_aligned(gamma, 16),
+                    (!gb_out || is_aligned(gb_out, 4 * dtype_size(gb_dtype))) && is_aligned(gamma, 16) &&
+                    (!gb_scale || is_aligned(gb_scale, 16)),
                 VITMI_E_ALIGN, "layernorm_bwd: pointer alignment");
   VITMI_REQUIRE(workspace && workspace_bytes >= vitmi_layernorm_bwd_workspace(M, D), VITMI_E_WORKSPACE, "layernorm_bwd: workspace too small");
   VITMI_REQUIRE(is_aligned(workspace, 16), VITMI_E_ALIGN, "layernorm_bwd: workspace alignment");
