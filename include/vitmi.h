@@ -288,6 +288,49 @@ int vitmi_lpi_bwd(const void* x, const void* u, const void* dout, const float* s
                   float* dgamma, float* dbeta, float* dw2, float* db2, int dtype, int training,
                   int64_t B, int64_t H, int64_t W, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------ conv stem --
+ * The stages of XCiT's ConvPatchEmbed (models/xcit.py:58-108): Conv2d(3x3, stride 2, padding 1, no bias) + BatchNorm2d, GELU
+ * (erf) between stages, on token-major activations [B, H*W, C] (C contiguous) in the compute dtype (bf16 or fp32).  The
+ * convolution is vitmi_conv3s2_im2col + vitmi_gemm; its data gradient is vitmi_gemm + vitmi_conv3s2_col2im.
+ *
+ * vitmi_conv3s2_im2col writes col [B*Ho*Wo, ld] (dtype), Ho = ceil(H/2), Wo = ceil(W/2): column k = c*9 + i*3 + j of row
+ *   (b, oy, ox) holds x[b, 2*oy-1+i, 2*ox-1+j, c], or zero outside the grid (vitmi_patchify's K order: a conv weight
+ *   [Cout, Cin, 3, 3] in its own memory is the k-major B operand).  ld >= 9*C, ld % 8 == 0; columns [9*C, ld) are written as
+ *   zeros.  image_form = 1: x is the fp32 image with element strides (sb, sc, sh, sw) (NCHW or channels_last), C = 3;
+ *   image_form = 0: x is token-major [B, H*W, C] in `dtype`, C a multiple of 8, 16-byte aligned (the strides are ignored).
+ *   A pure copy or cast.
+ * vitmi_conv3s2_col2im is its transpose in gather form (token-major only): dx[b, y, x, c] = the sum, in fp32 in a fixed
+ *   order, of the 1, 2 or 4 entries of dcol [B*Ho*Wo, ld] that read that pixel, stored once.  No atomics.
+ * vitmi_conv3s2_wcopy: dst[r, c] = src[r, c] for c < cols and 0 for cols <= c < dst_cols, r < rows (pitches in elements,
+ *   both `dtype`): the first stage's K = 27 weight as a [Cout, 32] image, and its gradient product's first 27 columns back.
+ * col, dcol, dx 16-byte aligned; B, H, W >= 1, B*H*W < 2^31.  Anything else fails before any launch.
+ *
+ * vitmi_bn_act_fwd / _bwd: BatchNorm over the rows of y [M, C] AS STORED in the compute dtype, then GELU if gelu != 0.
+ *   _fwd writes stat fp32 [2, C] = (mean, rstd) and out = act((y - mean) rstd gamma + beta) (compute dtype).  training:
+ *   mean and biased variance over the M rows, and, in place on the device, running_mean <- (1-m) running_mean + m mean,
+ *   running_var <- (1-m) running_var + m var M/(M-1), num_batches_tracked += 1 (any of the three may be null); eval: the
+ *   running buffers are read and nothing is touched.  _bwd, from dout, y, stat, gamma, beta: dz = dout gelu'(z) with z
+ *   recomputed (dz = dout without GELU), dbeta = sum dz, dgamma = sum dz yh (both STORED, fp32), dy = gamma rstd (dz -
+ *   dbeta/M - yh dgamma/M) in training, gamma rstd dz in eval (compute dtype; dy must not alias dout).  Statistics by Welford /
+ *   Chan in a fixed order, no atomics: bitwise repeatable.  C a multiple of 8, 1 <= M < 2^31, training needs M > 1; y, out,
+ *   dout, dy, stat, gamma, beta, dgamma, dbeta 16-byte aligned; the workspace (vitmi_bn_act_workspace bytes, 16-byte
+ *   aligned) is required.  Anything else fails before any launch.  All additive to ABI 109. */
+int vitmi_conv3s2_supported(int dtype, int image_form, int64_t B, int64_t H, int64_t W, int64_t C, int64_t ld);
+int vitmi_conv3s2_im2col(const void* x, int image_form, int64_t sb, int64_t sc, int64_t sh, int64_t sw, void* col,
+                         int dtype, int64_t ld, int64_t B, int64_t H, int64_t W, int64_t C, void* stream);
+int vitmi_conv3s2_col2im(const void* dcol, int64_t ld, void* dx, int dtype, int64_t B, int64_t H, int64_t W, int64_t C,
+                         void* stream);
+int vitmi_conv3s2_wcopy(const void* src, int64_t src_ld, void* dst, int64_t dst_ld, int dtype, int64_t rows, int64_t cols,
+                        int64_t dst_cols, void* stream);
+int vitmi_bn_act_supported(int dtype, int64_t M, int64_t C);
+size_t vitmi_bn_act_workspace(int dtype, int64_t M, int64_t C);
+int vitmi_bn_act_fwd(const void* y, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                     int64_t* num_batches_tracked, float* stat, void* out, int dtype, int gelu, int training,
+                     float momentum, float eps, int64_t M, int64_t C, void* workspace, size_t workspace_bytes, void* stream);
+int vitmi_bn_act_bwd(const void* dout, const void* y, const float* stat, const float* gamma, const float* beta, void* dy,
+                     float* dgamma, float* dbeta, int dtype, int gelu, int training, int64_t M, int64_t C,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------- CaiT ops --
  * Talking-heads softmax (models/cait.py:118-122) on score tensors [B,H,N,ld] (row length
  * Nk <= 1024 valid columns, H <= 16; other shapes fail with VITMI_E_SHAPE before any launch):

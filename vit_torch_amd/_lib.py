@@ -95,6 +95,15 @@ SIGNATURES = {
     "vitmi_lpi_workspace": (c_sz, [C.c_int, c_i64, c_i64, c_i64, c_i64]),
     "vitmi_lpi_fwd": (C.c_int, [c_vp] * 13 + [C.c_int, C.c_int, c_f32, c_f32, c_i64, c_i64, c_i64, c_i64, c_vp, c_sz, c_vp]),
     "vitmi_lpi_bwd": (C.c_int, [c_vp] * 16 + [C.c_int, C.c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_sz, c_vp]),
+    "vitmi_conv3s2_supported": (C.c_int, [C.c_int, C.c_int, c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "vitmi_conv3s2_im2col": (C.c_int, [c_vp, C.c_int, c_i64, c_i64, c_i64, c_i64, c_vp, C.c_int, c_i64, c_i64, c_i64, c_i64,
+                                       c_i64, c_vp]),
+    "vitmi_conv3s2_col2im": (C.c_int, [c_vp, c_i64, c_vp, C.c_int, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    "vitmi_conv3s2_wcopy": (C.c_int, [c_vp, c_i64, c_vp, c_i64, C.c_int, c_i64, c_i64, c_i64, c_vp]),
+    "vitmi_bn_act_supported": (C.c_int, [C.c_int, c_i64, c_i64]),
+    "vitmi_bn_act_workspace": (c_sz, [C.c_int, c_i64, c_i64]),
+    "vitmi_bn_act_fwd": (C.c_int, [c_vp] * 8 + [C.c_int, C.c_int, C.c_int, c_f32, c_f32, c_i64, c_i64, c_vp, c_sz, c_vp]),
+    "vitmi_bn_act_bwd": (C.c_int, [c_vp] * 8 + [C.c_int, C.c_int, C.c_int, c_i64, c_i64, c_vp, c_sz, c_vp]),
     "vitmi_attn_bwd_workspace": (c_sz, [c_i64, c_i64, c_i64]),
     "vitmi_attn_bwd_dbias_rows": (c_i64, [c_i64, c_i64]),
     "vitmi_attn_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_i64, c_i64, c_i64, c_i64,

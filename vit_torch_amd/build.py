@@ -40,11 +40,12 @@ SOURCES = [
     "attn_probs.hip",
     "xca.hip",
     "lpi.hip",
+    "convstem.hip",
     "cait_ops.hip",
     "cait_fused.hip",
     "swin_ops.hip",
 ]
-HEADERS = ["common.h", "epilogue.h", "gemm_tile.h", "../../include/vitmi.h"]
+HEADERS = ["common.h", "epilogue.h", "gemm_tile.h", "bnrows.h", "../../include/vitmi.h"]
 
 FLAGS = [
     f"--offload-arch={ARCH}",

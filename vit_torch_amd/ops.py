@@ -470,6 +470,128 @@ def lpi_bwd(x, u, dout, stat, w1, b1, gamma, beta, w2, dx, dw1, db1, dgamma, dbe
     return dx
 
 
+def conv3s2_supported(t, B, H, W, C, ld, *, image=False) -> bool:
+    """Host-only query: do conv3s2_im2col (image: its fp32-image form) / conv3s2_col2im take this compute dtype and shape?"""
+    return bool(load().vitmi_conv3s2_supported(dtype_code_or_neg(t), int(bool(image)), B, H, W, C, ld))
+
+
+def _conv3s2_check(who, t, B, H, W, C, ld, image):
+    """The supported query before anything else, so that an unsupported dtype or shape raises VitmiError with the library's
+    own message, and the col matrix's contract."""
+    if not conv3s2_supported(t, B, H, W, C, ld, image=image):
+        form = "image" if image else "token-major"
+        raise _lib.VitmiError(f"{who}: unsupported ({form} form needs bf16 or fp32, C {'== 3' if image else 'a multiple of 8'}, "
+                              f"ld a multiple of 8 and at least 9*C; got {t.dtype}, B {B}, H {H}, W {W}, C {C}, ld {ld})")
+    M = B * ((H + 1) // 2) * ((W + 1) // 2)
+    _contract(who, "col", t, t.dtype, M * ld, f"[B*Ho*Wo, ld] = [{M}, {ld}]")
+    return M
+
+
+def conv3s2_im2col(x, col, B, H, W, C):
+    """col [B*ceil(H/2)*ceil(W/2), ld] (bf16 or fp32) = the 3x3 / stride 2 / padding 1 windows of x, k = c*9 + i*3 + j, the
+    columns [9*C, ld) zero (vitmi_conv3s2_im2col).  x: the fp32 image [B, 3, H, W] in any strides (contiguous or
+    channels_last), or the token-major activation [B, H*W, C] in col's dtype with C a multiple of 8."""
+    _need_cuda(x, col)
+    image = x.dim() == 4
+    if col.dim() != 2:
+        raise _lib.VitmiError(f"conv3s2_im2col: col must be a 2-d [rows, ld] tensor, got {tuple(col.shape)}")
+    ld = col.shape[1]
+    _conv3s2_check("conv3s2_im2col", col, B, H, W, C, ld, image)
+    if image:
+        if x.dtype != torch.float32 or tuple(x.shape) != (B, C, H, W):
+            raise _lib.VitmiError(f"conv3s2_im2col: the image must be fp32 [B, C, H, W] = [{B}, {C}, {H}, {W}] "
+                                  f"(got {x.dtype}, {tuple(x.shape)})")
+        strides = x.stride()
+    else:
+        _contract("conv3s2_im2col", "x", x, col.dtype, B * H * W * C, f"[B, H*W, C] = [{B}, {H * W}, {C}]")
+        strides = (0, 0, 0, 0)
+    check(load().vitmi_conv3s2_im2col(x.data_ptr(), int(image), *strides, col.data_ptr(), dtype_code(col), ld, B, H, W, C,
+                                      _stream()), "vitmi_conv3s2_im2col")
+    return col
+
+
+def conv3s2_col2im(dcol, dx, B, H, W, C):
+    """dx [B, H*W, C] = the transpose of conv3s2_im2col's token-major form applied to dcol [B*Ho*Wo, ld]: each pixel sums,
+    in fp32 in a fixed order, the 1, 2 or 4 entries that read it (vitmi_conv3s2_col2im; no atomics)."""
+    _need_cuda(dcol, dx)
+    if dcol.dim() != 2:
+        raise _lib.VitmiError(f"conv3s2_col2im: dcol must be a 2-d [rows, ld] tensor, got {tuple(dcol.shape)}")
+    ld = dcol.shape[1]
+    _conv3s2_check("conv3s2_col2im", dcol, B, H, W, C, ld, False)
+    _contract("conv3s2_col2im", "dx", dx, dcol.dtype, B * H * W * C, f"[B, H*W, C] = [{B}, {H * W}, {C}]")
+    check(load().vitmi_conv3s2_col2im(dcol.data_ptr(), ld, dx.data_ptr(), dtype_code(dcol), B, H, W, C, _stream()),
+          "vitmi_conv3s2_col2im")
+    return dx
+
+
+def conv3s2_wcopy(src, dst, cols):
+    """dst[r, c] = src[r, c] for c < cols, 0 for the rest of dst's columns; src [rows, >= cols], dst [rows, >= cols], the same
+    dtype (vitmi_conv3s2_wcopy): the K = 27 weight of the first stage to its [Cout, 32] image, and its gradient back."""
+    _need_cuda(src, dst)
+    if (src.dim() != 2 or dst.dim() != 2 or src.dtype != dst.dtype or src.dtype not in (torch.bfloat16, torch.float32)
+            or src.shape[0] != dst.shape[0] or src.stride(1) != 1 or dst.stride(1) != 1 or cols > src.shape[1]
+            or cols > dst.shape[1]):
+        raise _lib.VitmiError(f"conv3s2_wcopy: src and dst must be 2-d bf16 or fp32 tensors of one dtype and row count with "
+                              f"at least {cols} columns (got {src.dtype} {tuple(src.shape)}, {dst.dtype} {tuple(dst.shape)})")
+    check(load().vitmi_conv3s2_wcopy(src.data_ptr(), src.stride(0), dst.data_ptr(), dst.stride(0), dtype_code(src),
+                                     src.shape[0], cols, dst.shape[1], _stream()), "vitmi_conv3s2_wcopy")
+    return dst
+
+
+def bn_act_supported(t, M, C) -> bool:
+    """Host-only query: do bn_act_fwd / bn_act_bwd take this dtype and shape?"""
+    return bool(load().vitmi_bn_act_supported(dtype_code_or_neg(t), M, C))
+
+
+def _bn_act_contract(who, y, acts, f32s, M, C):
+    if y.dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.VitmiError(f"{who}: y must be bf16 or fp32, got {y.dtype}")
+    for name, t in acts:
+        _contract(who, name, t, y.dtype, M * C, f"[M, C] = [{M}, {C}]")
+    for name, t, n in f32s:
+        if t is not None:
+            _contract(who, name, t, torch.float32, n, f"{n}-element")
+
+
+def bn_act_fwd(y, gamma, beta, running_mean, running_var, num_batches_tracked, stat, out, M, C, *, gelu, training,
+               momentum=0.1, eps=1e-5):
+    """out [M, C] = act(BatchNorm(y)) over the rows of y [M, C] (bf16 or fp32) as stored; act = GELU (erf) if `gelu`, else
+    nothing.  Writes stat fp32 [2, C] (mean, rstd), which bn_act_bwd needs.  training: batch statistics, and the three
+    running buffers (fp32 [C], fp32 [C], int64 [1]; each may be None) are updated on the device; otherwise the running
+    statistics are used and nothing is touched (vitmi_bn_act_fwd)."""
+    _need_cuda(y, gamma, beta, running_mean, running_var, num_batches_tracked, stat, out)
+    _bn_act_contract("bn_act_fwd", y, (("y", y), ("out", out)),
+                     (("weight", gamma, C), ("bias", beta, C), ("stat", stat, 2 * C), ("running_mean", running_mean, C),
+                      ("running_var", running_var, C)), M, C)
+    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1):
+        raise _lib.VitmiError("bn_act_fwd: num_batches_tracked must be an int64 tensor of one element")
+    if not training and (running_mean is None or running_var is None):
+        raise _lib.VitmiError("bn_act_fwd: eval mode needs running_mean and running_var")
+    code = dtype_code(y)
+    ptr, nb = _aligned_ws(load().vitmi_bn_act_workspace(code, M, C), y.device)
+    check(load().vitmi_bn_act_fwd(y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean), _ptr(running_var),
+                                  _ptr(num_batches_tracked), stat.data_ptr(), out.data_ptr(), code, int(bool(gelu)),
+                                  int(bool(training)), momentum, eps, M, C, ptr, nb, _stream()), "vitmi_bn_act_fwd")
+    return out
+
+
+def bn_act_bwd(dout, y, stat, gamma, beta, dy, dgamma, dbeta, M, C, *, gelu, training):
+    """Backward of bn_act_fwd: dy (compute dtype, not aliasing dout) and the fp32 dgamma, dbeta, stored, from dout, the
+    stored y and stat (vitmi_bn_act_bwd); training=False is the eval-mode gradient."""
+    _need_cuda(dout, y, stat, gamma, beta, dy, dgamma, dbeta)
+    _bn_act_contract("bn_act_bwd", y, (("y", y), ("dout", dout), ("dy", dy)),
+                     (("stat", stat, 2 * C), ("weight", gamma, C), ("bias", beta, C), ("dgamma", dgamma, C),
+                      ("dbeta", dbeta, C)), M, C)
+    if dy.data_ptr() == dout.data_ptr():
+        raise _lib.VitmiError("bn_act_bwd: dy must not alias dout")
+    code = dtype_code(y)
+    ptr, nb = _aligned_ws(load().vitmi_bn_act_workspace(code, M, C), y.device)
+    check(load().vitmi_bn_act_bwd(dout.data_ptr(), y.data_ptr(), stat.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                  dy.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), code, int(bool(gelu)),
+                                  int(bool(training)), M, C, ptr, nb, _stream()), "vitmi_bn_act_bwd")
+    return dy
+
+
 def attn_bwd_dbias_rows(B, N) -> int:
     return int(load().vitmi_attn_bwd_dbias_rows(B, N))
 
