@@ -331,6 +331,46 @@ int vitmi_bn_act_bwd(const void* dout, const void* y, const float* stat, const f
                      float* dgamma, float* dbeta, int dtype, int gelu, int training, int64_t M, int64_t C,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------- XCiT positional encoding and class-attention glue --
+ * (xcit_glue.hip; models/xcit.py:20-55 and :176-218.)  All additive to ABI 109.
+ *
+ * vitmi_posfourier_features: out [Hp*Wp, 2*hidden_dim] (`dtype`) = the sin / cos feature table of PositionalEncodingFourier
+ *   before its 1x1 projection, in the reference's channel order (hidden_dim y-features, then hidden_dim x-features, sin at
+ *   even and cos at odd indices) and operation order, for ONE image (the reference's mask is all-false, so the table does not
+ *   depend on the batch).  hidden_dim must be 32.
+ * vitmi_add_rows_bcast: out[b, n, :] = x[b, n, :] + pos[n, :]; x, out `dtype` [B, N, C], pos fp32 [N, C]; any N*C (a vector
+ *   tail is handled); x, pos, out 16-byte aligned.
+ *
+ * The class-attention block's glue.  Row 0 of every image is the CLS row; the residual stream (x, x1, xc, xp, out, G, dx1,
+ * dx2, dl) is fp32, the branch tensors (a [B, D], l [B, N1, D], m [B, D], da, gm) are `dtype`; gamma1, gamma2 fp32 [D].
+ * D a multiple of 8, N1 >= 2, every pointer 16-byte aligned.
+ *   vitmi_ca_merge_fwd: x1[b,n,:] = x[b,n,:] + gamma1 * (n == 0 ? a[b,:] : l[b,n,:]).
+ *   vitmi_ca_merge_bwd: da[b,:] = gamma1 * dx1[b,0,:]; dl[b,n,:] = n == 0 ? 0 : gamma1 * dx1[b,n,:] (STORED: the caller
+ *     accumulates the projections' data gradients onto it); dgamma1 (STORED) = sum_b dx1[b,0] a[b] + sum_{b,n>=1} dx1[b,n]
+ *     l[b,n], a two-level fp32 sum in a fixed order through the workspace (vitmi_ca_merge_bwd_workspace bytes, 16-byte
+ *     aligned), no atomics.
+ *   vitmi_ca_out_fwd: out[b,n,:] = n == 0 ? xc[b*xc_stride + :] + gamma2 * m[b,:] : 2 * xp[b,n,:]  (x_res + cat[gamma2
+ *     mlp(cls), x[:, 1:]]: the patch rows double).  xc_stride in elements, a multiple of 4.
+ *   vitmi_ca_out_bwd: dx2[b,n,:] = n == 0 ? G[b,0,:] : 2 G[b,n,:]; gm[b,:] = gamma2 * G[b,0,:].
+ * Anything else fails before any launch. */
+int vitmi_posfourier_supported(int dtype, int64_t Hp, int64_t Wp, int64_t hidden_dim);
+int vitmi_posfourier_features(void* out, int dtype, int64_t Hp, int64_t Wp, int64_t hidden_dim, float temperature,
+                              void* stream);
+int vitmi_add_rows_bcast_supported(int dtype, int64_t B, int64_t N, int64_t C);
+int vitmi_add_rows_bcast(const void* x, const float* pos, void* out, int dtype, int64_t B, int64_t N, int64_t C,
+                         void* stream);
+int vitmi_ca_glue_supported(int dtype, int64_t B, int64_t N1, int64_t D);
+int vitmi_ca_merge_fwd(const float* x, const void* a, const void* l, const float* gamma1, float* x1, int dtype,
+                       int64_t B, int64_t N1, int64_t D, void* stream);
+size_t vitmi_ca_merge_bwd_workspace(int64_t B, int64_t N1, int64_t D);
+int vitmi_ca_merge_bwd(const float* dx1, const void* l, const void* a, const float* gamma1, void* da, float* dl,
+                       float* dgamma1, int dtype, int64_t B, int64_t N1, int64_t D, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int vitmi_ca_out_fwd(const float* xc, int64_t xc_stride, const float* xp, const void* m, const float* gamma2,
+                     float* out, int dtype, int64_t B, int64_t N1, int64_t D, void* stream);
+int vitmi_ca_out_bwd(const float* G, const float* gamma2, float* dx2, void* gm, int dtype, int64_t B, int64_t N1,
+                     int64_t D, void* stream);
+
 /* ------------------------------------------------------------- CaiT ops --
  * Talking-heads softmax (models/cait.py:118-122) on score tensors [B,H,N,ld] (row length
  * Nk <= 1024 valid columns, H <= 16; other shapes fail with VITMI_E_SHAPE before any launch):

@@ -104,6 +104,16 @@ SIGNATURES = {
     "vitmi_bn_act_workspace": (c_sz, [C.c_int, c_i64, c_i64]),
     "vitmi_bn_act_fwd": (C.c_int, [c_vp] * 8 + [C.c_int, C.c_int, C.c_int, c_f32, c_f32, c_i64, c_i64, c_vp, c_sz, c_vp]),
     "vitmi_bn_act_bwd": (C.c_int, [c_vp] * 8 + [C.c_int, C.c_int, C.c_int, c_i64, c_i64, c_vp, c_sz, c_vp]),
+    "vitmi_posfourier_supported": (C.c_int, [C.c_int, c_i64, c_i64, c_i64]),
+    "vitmi_posfourier_features": (C.c_int, [c_vp, C.c_int, c_i64, c_i64, c_i64, c_f32, c_vp]),
+    "vitmi_add_rows_bcast_supported": (C.c_int, [C.c_int, c_i64, c_i64, c_i64]),
+    "vitmi_add_rows_bcast": (C.c_int, [c_vp, c_vp, c_vp, C.c_int, c_i64, c_i64, c_i64, c_vp]),
+    "vitmi_ca_glue_supported": (C.c_int, [C.c_int, c_i64, c_i64, c_i64]),
+    "vitmi_ca_merge_fwd": (C.c_int, [c_vp] * 5 + [C.c_int, c_i64, c_i64, c_i64, c_vp]),
+    "vitmi_ca_merge_bwd_workspace": (c_sz, [c_i64, c_i64, c_i64]),
+    "vitmi_ca_merge_bwd": (C.c_int, [c_vp] * 7 + [C.c_int, c_i64, c_i64, c_i64, c_vp, c_sz, c_vp]),
+    "vitmi_ca_out_fwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, C.c_int, c_i64, c_i64, c_i64, c_vp]),
+    "vitmi_ca_out_bwd": (C.c_int, [c_vp] * 4 + [C.c_int, c_i64, c_i64, c_i64, c_vp]),
     "vitmi_attn_bwd_workspace": (c_sz, [c_i64, c_i64, c_i64]),
     "vitmi_attn_bwd_dbias_rows": (c_i64, [c_i64, c_i64]),
     "vitmi_attn_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_i64, c_i64, c_i64, c_i64,

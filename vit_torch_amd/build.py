@@ -41,6 +41,7 @@ SOURCES = [
     "xca.hip",
     "lpi.hip",
     "convstem.hip",
+    "xcit_glue.hip",
     "cait_ops.hip",
     "cait_fused.hip",
     "swin_ops.hip",

@@ -592,6 +592,114 @@ def bn_act_bwd(dout, y, stat, gamma, beta, dy, dgamma, dbeta, M, C, *, gelu, tra
     return dy
 
 
+def posfourier_supported(t, Hp, Wp, hidden_dim) -> bool:
+    """Host-only query: does posfourier_features build this table (bf16 or fp32, hidden_dim 32)?"""
+    return bool(load().vitmi_posfourier_supported(dtype_code_or_neg(t), Hp, Wp, hidden_dim))
+
+
+def posfourier_features(out, Hp, Wp, hidden_dim=32, temperature=10000.0):
+    """out [Hp*Wp, 2*hidden_dim] (bf16 or fp32) = the sin / cos feature table of XCiT's PositionalEncodingFourier before its
+    1x1 projection: hidden_dim y-features then hidden_dim x-features, sin at even and cos at odd indices, for one image
+    (vitmi_posfourier_features).  hidden_dim must be 32."""
+    _need_cuda(out)
+    if not posfourier_supported(out, Hp, Wp, hidden_dim):
+        raise _lib.VitmiError(f"posfourier_features: unsupported (needs bf16 or fp32, hidden_dim 32, a grid of at least 1 x 1; "
+                              f"got {out.dtype}, hidden_dim {hidden_dim}, grid {Hp} x {Wp})")
+    _contract("posfourier_features", "out", out, out.dtype, Hp * Wp * 2 * hidden_dim,
+              f"[Hp*Wp, 2*hidden_dim] = [{Hp * Wp}, {2 * hidden_dim}]")
+    check(load().vitmi_posfourier_features(out.data_ptr(), dtype_code(out), Hp, Wp, hidden_dim, float(temperature), _stream()),
+          "vitmi_posfourier_features")
+    return out
+
+
+def add_rows_bcast_supported(t, B, N, C) -> bool:
+    """Host-only query: does add_rows_bcast take this dtype and shape?"""
+    return bool(load().vitmi_add_rows_bcast_supported(dtype_code_or_neg(t), B, N, C))
+
+
+def add_rows_bcast(x, pos, out, B, N, C):
+    """out[b, n, :] = x[b, n, :] + pos[n, :]: x, out [B, N, C] in one dtype (bf16 or fp32), pos fp32 [N, C]
+    (vitmi_add_rows_bcast)."""
+    _need_cuda(x, pos, out)
+    if not add_rows_bcast_supported(x, B, N, C):
+        raise _lib.VitmiError(f"add_rows_bcast: unsupported (needs bf16 or fp32 and B, N, C >= 1; got {x.dtype}, B {B}, N {N}, C {C})")
+    _contract("add_rows_bcast", "x", x, x.dtype, B * N * C, f"[B, N, C] = [{B}, {N}, {C}]")
+    _contract("add_rows_bcast", "out", out, x.dtype, B * N * C, f"[B, N, C] = [{B}, {N}, {C}]")
+    _contract("add_rows_bcast", "pos", pos, torch.float32, N * C, f"[N, C] = [{N}, {C}]")
+    check(load().vitmi_add_rows_bcast(x.data_ptr(), pos.data_ptr(), out.data_ptr(), dtype_code(x), B, N, C, _stream()),
+          "vitmi_add_rows_bcast")
+    return out
+
+
+def ca_glue_supported(t, B, N1, D) -> bool:
+    """Host-only query: do ca_merge_fwd / ca_merge_bwd / ca_out_fwd / ca_out_bwd take this operand dtype and shape?"""
+    return bool(load().vitmi_ca_glue_supported(dtype_code_or_neg(t), B, N1, D))
+
+
+def _ca_contract(who, op, B, N1, D, res=(), rows=(), cls=(), vecs=()):
+    """The class-attention glue's contracts: `op` (a [B, D] operand) fixes the operand dtype; `res` (name, tensor) are fp32
+    [B, N1, D]; `rows` operand-dtype [B, N1, D]; `cls` operand-dtype [B, D]; `vecs` fp32 [D]."""
+    if not ca_glue_supported(op, B, N1, D):
+        raise _lib.VitmiError(f"{who}: unsupported (needs bf16 or fp32 operands, N1 >= 2 and D a multiple of 8; got {op.dtype}, "
+                              f"B {B}, N1 {N1}, D {D})")
+    for name, t in res:
+        _contract(who, name, t, torch.float32, B * N1 * D, f"[B, N1, D] = [{B}, {N1}, {D}]")
+    for name, t in rows:
+        _contract(who, name, t, op.dtype, B * N1 * D, f"[B, N1, D] = [{B}, {N1}, {D}]")
+    for name, t in cls:
+        _contract(who, name, t, op.dtype, B * D, f"[B, D] = [{B}, {D}]")
+    for name, t in vecs:
+        _contract(who, name, t, torch.float32, D, f"[D] = [{D}]")
+
+
+def ca_merge_fwd(x, a, l, gamma1, x1, B, N1, D):
+    """x1[b, n, :] = x[b, n, :] + gamma1 * (n == 0 ? a[b, :] : l[b, n, :]): the first residual of XCiT's class-attention
+    block, whose attention returns cat[proj(cls), norm1(x)[:, 1:]].  x, x1 fp32; a [B, D], l [B, N1, D] bf16 or fp32."""
+    _need_cuda(x, a, l, gamma1, x1)
+    _ca_contract("ca_merge_fwd", a, B, N1, D, res=(("x", x), ("x1", x1)), rows=(("l", l),), cls=(("a", a),),
+                 vecs=(("gamma1", gamma1),))
+    check(load().vitmi_ca_merge_fwd(x.data_ptr(), a.data_ptr(), l.data_ptr(), gamma1.data_ptr(), x1.data_ptr(), dtype_code(a),
+                                    B, N1, D, _stream()), "vitmi_ca_merge_fwd")
+    return x1
+
+
+def ca_merge_bwd(dx1, l, a, gamma1, da, dl, dgamma1, B, N1, D):
+    """Backward of ca_merge_fwd's branch: da [B, D] = gamma1 * dx1[:, 0] (operand dtype); dl fp32 [B, N1, D] = gamma1 *
+    dx1 on the patch rows and 0 on the CLS rows (stored: accumulate the projections' data gradients onto it); dgamma1 fp32
+    [D], stored, summed over every row against a (row 0) or l (the rest) in two levels without atomics."""
+    _need_cuda(dx1, l, a, gamma1, da, dl, dgamma1)
+    _ca_contract("ca_merge_bwd", a, B, N1, D, res=(("dx1", dx1), ("dl", dl)), rows=(("l", l),), cls=(("a", a), ("da", da)),
+                 vecs=(("gamma1", gamma1), ("dgamma1", dgamma1)))
+    ptr, nb = _aligned_ws(load().vitmi_ca_merge_bwd_workspace(B, N1, D), dx1.device)
+    check(load().vitmi_ca_merge_bwd(dx1.data_ptr(), l.data_ptr(), a.data_ptr(), gamma1.data_ptr(), da.data_ptr(), dl.data_ptr(),
+                                    dgamma1.data_ptr(), dtype_code(a), B, N1, D, ptr, nb, _stream()), "vitmi_ca_merge_bwd")
+    return dl
+
+
+def ca_out_fwd(xc, xp, m, gamma2, out, B, N1, D):
+    """out[b, n, :] = n == 0 ? xc[b, :] + gamma2 * m[b, :] : 2 * xp[b, n, :]: the block's last line, x_res + cat[gamma2 *
+    mlp(cls), x[:, 1:]].  xc: the normed CLS rows, an fp32 [B, D] tensor or view with unit column stride (row 0 of each
+    image of norm2's output, or its compact output); xp fp32 [B, N1, D] holds the patch rows; m [B, D] bf16 or fp32."""
+    _need_cuda(xc, xp, m, gamma2, out)
+    _ca_contract("ca_out_fwd", m, B, N1, D, res=(("xp", xp), ("out", out)), cls=(("m", m),), vecs=(("gamma2", gamma2),))
+    if xc.dtype != torch.float32 or tuple(xc.shape) != (B, D) or xc.stride(1) != 1:
+        raise _lib.VitmiError(f"ca_out_fwd: xc must be an fp32 [B, D] = [{B}, {D}] tensor or row view (got {xc.dtype}, "
+                              f"{tuple(xc.shape)}, strides {xc.stride()})")
+    check(load().vitmi_ca_out_fwd(xc.data_ptr(), xc.stride(0) if B > 1 else D, xp.data_ptr(), m.data_ptr(), gamma2.data_ptr(),
+                                  out.data_ptr(), dtype_code(m), B, N1, D, _stream()), "vitmi_ca_out_fwd")
+    return out
+
+
+def ca_out_bwd(G, gamma2, dx2, gm, B, N1, D):
+    """Backward of ca_out_fwd without the MLP: dx2[b, n, :] = n == 0 ? G[b, 0, :] : 2 * G[b, n, :] (fp32) and gm [B, D] =
+    gamma2 * G[:, 0] in the operand dtype (gm's), the gradient that enters the MLP."""
+    _need_cuda(G, gamma2, dx2, gm)
+    _ca_contract("ca_out_bwd", gm, B, N1, D, res=(("G", G), ("dx2", dx2)), cls=(("gm", gm),), vecs=(("gamma2", gamma2),))
+    check(load().vitmi_ca_out_bwd(G.data_ptr(), gamma2.data_ptr(), dx2.data_ptr(), gm.data_ptr(), dtype_code(gm), B, N1, D,
+                                  _stream()), "vitmi_ca_out_bwd")
+    return dx2
+
+
 def attn_bwd_dbias_rows(B, N) -> int:
     return int(load().vitmi_attn_bwd_dbias_rows(B, N))
 

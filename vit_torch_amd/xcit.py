@@ -1,5 +1,5 @@
-"""XCiT's cross-covariance attention (XCA), local patch interaction (LPI) and convolutional patch embedding (ConvPatchEmbed)
-on libvitmi kernels.
+"""XCiT's cross-covariance attention (XCA), local patch interaction (LPI), convolutional patch embedding (ConvPatchEmbed),
+Fourier positional encoding (PositionalEncodingFourier) and class-attention block (ClassAttentionBlock) on libvitmi kernels.
 
 `XCA` is the attention module of the reference's `models/xcit.py:221-261`: a qkv Linear, attention over CHANNELS
 (q and k L2-normalised along the token axis, a learnable per-head temperature, a softmax over an hd x hd map per head)
@@ -19,7 +19,20 @@ BatchNorm + GELU is `ops.bn_act_fwd` / `ops.bn_act_bwd`.  Activations are token-
 the first stage on: no NCHW tensor exists after the image.  State-dict keys are the reference's (`proj.{0,2,4,6}.0.weight`,
 `proj.{0,2,4,6}.1.*`).  Batch statistics are per process, as LPI's.  The gradient with respect to the image is not built.
 
-The rest of XCiT (the Fourier positional encoding, XCiT's class-attention blocks, an engine) is not built.
+`PositionalEncodingFourier` is the reference's `models/xcit.py:20-55` as `XCiT.forward_features` uses it: `x + pos` on the
+token-major tensor.  A sin / cos feature table for one image (`ops.posfourier_features`, `xcit_glue.hip`; cached, it depends
+on no parameter), its 1x1-conv projection as a product on the library's GEMM with the conv weight's own memory as the operand,
+and an add that broadcasts over the batch (`ops.add_rows_bcast`).  State-dict keys are the reference's
+(`token_projection.weight [dim, 64, 1, 1]`, `token_projection.bias`).
+
+`ClassAttentionBlock` is the reference's `models/xcit.py:144-218` (its `ClassAttention` inside): LayerNorm, class attention
+(one query per head over all tokens: `ops.class_attn_fwd` / `class_attn_bwd`, reading k and v in place), LayerScale residual,
+LayerNorm on every token or on the CLS token only (`tokens_norm`), an MLP on the CLS token, and the reference's last line,
+which doubles the patch rows.  The element-wise steps between the GEMMs are the `ops.ca_*` kernels (`xcit_glue.hip`).
+State-dict keys are the reference's (`norm1.*`, `attn.qkv.*`, `attn.proj.*`, `norm2.*`, `mlp.fc1.*`, `mlp.fc2.*`, `gamma1`,
+`gamma2`).
+
+Of XCiT, only the engine that composes these modules (and its zoo entry) is not built.
 
 Stand-alone modules on `engine.PackedModule`, as `ClassifierHead` is: the parameters live in a `ParamPack` (the fused
 optimizers update them), forward and backward run through the mixin's one `torch.autograd.Function`; each class here
@@ -27,7 +40,9 @@ keeps its constructor, its input checks and its `_forward` / `_backward`.  XCA: 
 `ops.xca_bwd` and `ops.colsum`.  compute_dtype "bf16": bf16 activations between the stages, GEMMs on the pack's bf16 weight
 shadows; "fp32": everything in fp32.  LPI: bf16 or fp32 activations, every parameter and parameter gradient in fp32.
 ConvPatchEmbed: bf16 or fp32 activations, the GEMMs on the bf16 weight shadows in "bf16", the norm parameters and every
-gradient in fp32.  CPU tensors raise: there is no fallback.
+gradient in fp32.  PositionalEncodingFourier: the feature table and the GEMM operands in the compute dtype, the encoding,
+the sum and every gradient in fp32.  ClassAttentionBlock: the residual stream in fp32, the branch tensors and GEMM operands
+in the compute dtype.  CPU tensors raise: there is no fallback.
 """
 from __future__ import annotations
 
@@ -35,8 +50,22 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import VitmiError
+from ._lib import EPI_BIAS_GELU, EPI_DGELU, VitmiError
 from .engine import PackedModule
+
+
+def _gemm_dw(dy, col, gw, min_rows=1024):
+    """gw [Cout, K] = dy^T col, a sum over the M rows.  In "fp32" the sum is taken in two levels, at most 64 row chunks
+    of at least `min_rows` rows accumulated into gw: a single fp32 accumulation over the 10^4 .. 10^6 rows of the conv stem's
+    early stages or of a batch of token rows carries an error that grows with sqrt(M), which the two levels cut to about
+    sqrt(M / 64) + 8.  "bf16" keeps one product: its operands' rounding dominates."""
+    M = dy.shape[0]
+    if dy.dtype != torch.float32 or M <= min_rows:
+        return ops.gemm(dy, col, gw, a_kmajor=False, b_kmajor=False)
+    R = max(min_rows, (-(-M // 64) + 63) // 64 * 64)
+    for r in range(0, M, R):
+        ops.gemm(dy[r:r + R], col[r:r + R], gw, a_kmajor=False, b_kmajor=False, accumulate=r > 0)
+    return gw
 
 
 class XCA(PackedModule, nn.Module):
@@ -237,19 +266,6 @@ class ConvPatchEmbed(PackedModule, nn.Module):
         for r in range(0, A.shape[0], self.ROW_CHUNK):
             ops.gemm(A[r:r + self.ROW_CHUNK], Bm, C[r:r + self.ROW_CHUNK], **k)
 
-    def _gemm_dw(self, dy, col, gw):
-        """gw [Cout, K] = dy^T col, a sum over the M rows.  In "fp32" the sum is taken in two levels, at most 64 row chunks
-        of at least 1024 rows accumulated into gw: a single fp32 accumulation over the 10^5 .. 10^6 rows of the early stages
-        carries an error that grows with sqrt(M), which the two levels cut to about sqrt(M / 64) + 8.  "bf16" keeps one
-        product: its operands' rounding dominates."""
-        M = dy.shape[0]
-        if dy.dtype != torch.float32 or M <= 1024:
-            return ops.gemm(dy, col, gw, a_kmajor=False, b_kmajor=False)
-        R = max(1024, (-(-M // 64) + 63) // 64 * 64)
-        for r in range(0, M, R):
-            ops.gemm(dy[r:r + R], col[r:r + R], gw, a_kmajor=False, b_kmajor=False, accumulate=r > 0)
-        return gw
-
     def _forward(self, x, save):
         pk = self._pack
         dt = torch.bfloat16 if self.compute_dtype == "bf16" else torch.float32
@@ -296,11 +312,255 @@ class ConvPatchEmbed(PackedModule, nn.Module):
             ops.conv3s2_im2col(inp, col, B, h, w, ci)
             if s == 0:
                 gimg = torch.empty((co, 32), dtype=torch.float32, device=y.device)
-                self._gemm_dw(dy, col, gimg)
+                _gemm_dw(dy, col, gimg)
                 ops.conv3s2_wcopy(gimg, pk.g(conv.weight).view(co, 27), 27)
                 break
-            self._gemm_dw(dy, col, pk.g(conv.weight).view(co, 9 * ci))
+            _gemm_dw(dy, col, pk.g(conv.weight).view(co, 9 * ci))
             self._gemm_rows(dy, pk.w(conv.weight).view(co, 9 * ci), col, b_kmajor=False)    # dcol, over col: it is done with
             d = torch.empty((B * h * w, ci), dtype=dt, device=y.device)
             ops.conv3s2_col2im(col, d, B, h, w, ci)
         return None
+
+
+class PositionalEncodingFourier(PackedModule, nn.Module):
+    """`forward(x, H, W)` with x [B, H*W, dim] returns `x + pos` in fp32, pos [H*W, dim] being the reference's encoding of an
+    H x W grid: how `XCiT.forward_features` uses it (`x = x + pos_embeder(B, Hp, Wp).reshape(B, -1, N).permute(0, 2, 1)`).
+    The reference's own `forward(B, H, W) -> [B, dim, H, W]` would materialise B identical NCHW copies of the encoding and is
+    not built.  `table(H, W)` returns the fp32 encoding [H*W, dim] under no_grad.  `token_projection` only holds the
+    parameters under the reference's names; it is never called.  x gets `dx = dout` (the same tensor).
+
+    Kept for the backward: nothing but the grid; the feature table is cached per (H, W, dtype, device)."""
+
+    def __init__(self, hidden_dim=32, dim=768, temperature=10000, compute_dtype="bf16"):
+        super().__init__()
+        if compute_dtype not in ("bf16", "fp32"):
+            raise VitmiError(f"PositionalEncodingFourier: compute_dtype must be 'bf16' or 'fp32', got {compute_dtype!r}")
+        if hidden_dim != 32:
+            raise VitmiError(f"PositionalEncodingFourier: hidden_dim {hidden_dim} is not built (the reference's XCiT uses 32)")
+        if dim < 8 or dim % 8:
+            raise VitmiError(f"PositionalEncodingFourier: dim = {dim} must be a multiple of 8")
+        if not temperature > 0:
+            raise VitmiError(f"PositionalEncodingFourier: the temperature must be positive, got {temperature}")
+        self.token_projection = nn.Conv2d(hidden_dim * 2, dim, kernel_size=1)
+        self.hidden_dim, self.dim, self.temperature, self.compute_dtype = hidden_dim, dim, temperature, compute_dtype
+        self.pack_shadow = compute_dtype == "bf16"        # the projection reads the bf16 weight shadow
+        self._tables = {}
+
+    def _check(self, x, H, W):
+        self._refuse_cpu(x)
+        if x.dim() != 3 or x.shape[-1] != self.dim:
+            raise VitmiError(f"PositionalEncodingFourier: input must be [B, H*W, {self.dim}], got {tuple(x.shape)}")
+        if H < 1 or W < 1 or x.shape[1] != H * W:
+            raise VitmiError(f"PositionalEncodingFourier: {x.shape[1]} tokens are not an H x W = {H} x {W} grid")
+
+    def forward(self, x, H, W):
+        self._check(x, H, W)
+        return self._run(x, H, W)
+
+    def table(self, H, W):
+        """the encoding [H*W, dim] in fp32 (no gradient)"""
+        self.engine()
+        with torch.no_grad():
+            return self._pos(H, W, self._pack.params[0].device)
+
+    # ---- kernels
+    def _features(self, H, W, dev):
+        dt = torch.bfloat16 if self.compute_dtype == "bf16" else torch.float32
+        key = (H, W, dt, str(dev))
+        f = self._tables.get(key)
+        if f is None:
+            f = torch.empty((H * W, 2 * self.hidden_dim), dtype=dt, device=dev)
+            ops.posfourier_features(f, H, W, self.hidden_dim, self.temperature)
+            self._tables[key] = f
+        return f
+
+    def _pos(self, H, W, dev):
+        pk, tp = self._pack, self.token_projection
+        pk.refresh_shadow()
+        pos = torch.empty((H * W, self.dim), dtype=torch.float32, device=dev)
+        return ops.gemm(self._features(H, W, dev), pk.w(tp.weight).view(self.dim, 2 * self.hidden_dim), pos, bias=pk.f32(tp.bias))
+
+    def _forward(self, x, H, W, save):
+        B, N, C = x.shape
+        xa = x.float().contiguous()
+        out = ops.add_rows_bcast(xa, self._pos(H, W, x.device), torch.empty_like(xa), B, N, C)
+        if save:
+            self._saved = (H, W)
+        return out
+
+    def _backward(self, dout, need_dx):
+        H, W = self._take_saved()
+        pk, tp, C = self._pack, self.token_projection, self.dim
+        d = dout.float().contiguous()
+        B, N = d.shape[0], H * W
+        dpos = torch.empty((N, C), dtype=torch.float32, device=d.device)
+        ops.colsum(d, dpos, M=B, N=N * C)
+        ops.colsum(dpos, pk.g(tp.bias), M=N, N=C)
+        feat = self._features(H, W, d.device)
+        dp = dpos if feat.dtype == torch.float32 else ops.cast(dpos, torch.empty_like(dpos, dtype=feat.dtype))
+        ops.gemm(dp, feat, pk.g(tp.weight).view(C, 2 * self.hidden_dim), a_kmajor=False, b_kmajor=False)
+        return dout if need_dx else None
+
+
+class _ParamHolder(nn.Module):
+    """holds Linear layers under the reference's names; never called"""
+
+    def forward(self, *a, **k):
+        raise VitmiError("this submodule only holds parameters; call the ClassAttentionBlock")
+
+
+class ClassAttentionBlock(PackedModule, nn.Module):
+    """XCiT's class-attention block: `forward(x, H, W, mask=None)` with x [B, 1 + Np, dim], CLS first, returns the fp32
+    [B, 1 + Np, dim] tensor of the reference's block; H, W and mask are accepted and unused, as there.  The patch rows do
+    change: they receive `x + gamma1 * norm1(x)`, are normed by norm2 if `tokens_norm`, and are doubled by the block's last
+    line.  `attn` (`qkv`, `proj`) and `mlp` (`fc1`, `fc2`) only hold parameters under the reference's names.  The reference
+    computes q for every token and uses the CLS row's only, so q is computed for the CLS rows alone; the patch rows' share of
+    the q weight gradient is exactly zero.
+
+    Kept for the backward: x (fp32), l = norm1(x) and [k v] (compute dtype, all rows), both norms' statistics, x1 (fp32),
+    and per image: q, the attention output, its softmax, the projected CLS token a, the normed CLS row, the MLP's
+    pre-activation (its gelu' in "bf16") and hidden row, and m = mlp(cls)."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, qk_scale=None, drop=0., attn_drop=0., drop_path=0.,
+                 act_layer=nn.GELU, norm_layer=nn.LayerNorm, eta=None, tokens_norm=False, compute_dtype="bf16"):
+        super().__init__()
+        if compute_dtype not in ("bf16", "fp32"):
+            raise VitmiError(f"ClassAttentionBlock: compute_dtype must be 'bf16' or 'fp32', got {compute_dtype!r}")
+        if drop != 0. or attn_drop != 0. or drop_path != 0.:
+            raise VitmiError("ClassAttentionBlock: dropout and drop_path are not built")
+        if act_layer is not nn.GELU:
+            raise VitmiError("ClassAttentionBlock: only nn.GELU (erf form) is built as the activation")
+        if eta is None:
+            raise VitmiError("ClassAttentionBlock: eta=None (no LayerScale) is not built: every XCiT factory of the reference "
+                             "passes an eta")
+        if dim % num_heads or dim // num_heads > 64 or (dim // num_heads) % 8:
+            raise VitmiError(f"ClassAttentionBlock: head dim {dim}/{num_heads} must be a multiple of 8, at most 64")
+        self.dim, self.num_heads, self.compute_dtype, self.tokens_norm = dim, num_heads, compute_dtype, tokens_norm
+        self.scale = qk_scale or (dim // num_heads) ** -0.5
+        self.norm1 = norm_layer(dim)
+        self.attn = _ParamHolder()
+        self.attn.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
+        self.attn.proj = nn.Linear(dim, dim)
+        self.norm2 = norm_layer(dim)
+        self.mlp = _ParamHolder()
+        self.mlp.fc1 = nn.Linear(dim, int(dim * mlp_ratio))
+        self.mlp.fc2 = nn.Linear(int(dim * mlp_ratio), dim)
+        for n in (self.norm1, self.norm2):
+            if not isinstance(n, nn.LayerNorm) or not n.elementwise_affine or tuple(n.normalized_shape) != (dim,):
+                raise VitmiError("ClassAttentionBlock: norm_layer must build an affine nn.LayerNorm over dim")
+        if int(dim * mlp_ratio) < 8 or int(dim * mlp_ratio) % 8:
+            raise VitmiError(f"ClassAttentionBlock: the MLP's hidden width {int(dim * mlp_ratio)} must be a multiple of 8")
+        self.gamma1 = nn.Parameter(eta * torch.ones(dim))
+        self.gamma2 = nn.Parameter(eta * torch.ones(dim))
+        self.pack_shadow = compute_dtype == "bf16"        # the GEMMs read the bf16 weight shadows
+
+    MAX_TOKENS = 1025       # ops.class_attn_fwd / class_attn_bwd
+
+    def forward(self, x, H, W, mask=None):
+        self._refuse_cpu(x)
+        if x.dim() != 3 or x.shape[-1] != self.dim or x.shape[1] < 2:
+            raise VitmiError(f"ClassAttentionBlock: input must be [B, 1 + Np, {self.dim}] with at least one patch, got "
+                             f"{tuple(x.shape)}")
+        if x.shape[1] > self.MAX_TOKENS:
+            raise VitmiError(f"ClassAttentionBlock: {x.shape[1]} tokens: the class-attention kernels take at most {self.MAX_TOKENS}")
+        return self._run(x)
+
+    # ---- kernels
+    def _forward(self, x, save):
+        B, N1, D = x.shape
+        H, hd, pk, M = self.num_heads, D // self.num_heads, self._pack, B * N1
+        a_, mlp, dev, f32 = self.attn, self.mlp, x.device, torch.float32
+        T = torch.bfloat16 if self.compute_dtype == "bf16" else f32
+        new = lambda *shape, dtype=T: torch.empty(shape, dtype=dtype, device=dev)      # noqa: E731
+        pk.refresh_shadow()
+        xa = x.float().contiguous()
+        l, mean1, rstd1 = new(M, D), new(M, dtype=f32), new(M, dtype=f32)
+        ops.layernorm_fwd(xa, pk.f32(self.norm1.weight), pk.f32(self.norm1.bias), l, mean1, rstd1, self.norm1.eps, M=M, D=D)
+        Wqkv, bqkv = pk.w(a_.qkv.weight), (pk.f32(a_.qkv.bias) if a_.qkv.bias is not None else None)
+        kv = new(M, 2 * D)
+        ops.gemm(l, Wqkv[D:], kv, bias=bqkv[D:] if bqkv is not None else None)
+        q = new(B, D)
+        ops.gemm(l.view(B, N1 * D)[:, :D], Wqkv[:D], q, bias=bqkv[:D] if bqkv is not None else None)
+        o, psave = new(B, D), new(B * H * N1, dtype=f32)
+        ops.class_attn_fwd(q, kv, kv[:, D:], 2 * D, o, psave, B, H, N1, hd, self.scale)
+        a = new(B, D)
+        ops.gemm(o, pk.w(a_.proj.weight), a, bias=pk.f32(a_.proj.bias))
+        x1 = ops.ca_merge_fwd(xa, a, l, pk.f32(self.gamma1), new(B, N1, D, dtype=f32), B, N1, D)
+        g2, b2 = pk.f32(self.norm2.weight), pk.f32(self.norm2.bias)
+        if self.tokens_norm:
+            x2, mean2, rstd2 = new(B, N1, D, dtype=f32), new(M, dtype=f32), new(M, dtype=f32)
+            ops.layernorm_fwd(x1, g2, b2, x2, mean2, rstd2, self.norm2.eps, M=M, D=D)
+            xc, xp = x2.view(B, N1 * D)[:, :D], x2
+        else:
+            xc, mean2, rstd2 = new(B, D, dtype=f32), new(B, dtype=f32), new(B, dtype=f32)
+            ops.layernorm_fwd(x1, g2, b2, xc, mean2, rstd2, self.norm2.eps, M=B, D=D, x_stride=N1 * D)
+            xp = x1
+        # the MLP's operand: the normed CLS rows, compact, in the compute dtype (kept for the fc1 weight gradient)
+        xcT = xc if T == f32 and not self.tokens_norm else ops.scale_cast(xc, new(B, D), M=B, N=D, ldx=N1 * D if self.tokens_norm else D)
+        Dh = mlp.fc1.out_features
+        pre = new(B, Dh) if save else None
+        hid = new(B, Dh)
+        ops.gemm(xcT, pk.w(mlp.fc1.weight), hid, epilogue=EPI_BIAS_GELU, bias=pk.f32(mlp.fc1.bias), C2=pre,
+                 aux_deriv=T == torch.bfloat16)
+        m = new(B, D)
+        ops.gemm(hid, pk.w(mlp.fc2.weight), m, bias=pk.f32(mlp.fc2.bias))
+        out = ops.ca_out_fwd(xc, xp, m, pk.f32(self.gamma2), new(B, N1, D, dtype=f32), B, N1, D)
+        if save:
+            self._saved = (xa, l, mean1, rstd1, kv, q, o, psave, a, x1, mean2, rstd2, xcT, pre, hid, m)
+        return out
+
+    def _backward(self, dout, need_dx):
+        xa, l, mean1, rstd1, kv, q, o, psave, a, x1, mean2, rstd2, xcT, pre, hid, m = self._take_saved()
+        B, N1, D = xa.shape
+        H, hd, pk, M = self.num_heads, D // self.num_heads, self._pack, B * N1
+        a_, mlp, dev, f32, T = self.attn, self.mlp, xa.device, torch.float32, l.dtype
+        new = lambda *shape, dtype=T: torch.empty(shape, dtype=dtype, device=dev)      # noqa: E731
+        G = dout.float().contiguous()
+        Gc = G.view(B, N1 * D)[:, :D]                       # the CLS rows, strided
+        # the last line and the MLP on B rows
+        dx2, gm = new(B, N1, D, dtype=f32), new(B, D)
+        ops.ca_out_bwd(G, pk.f32(self.gamma2), dx2, gm, B, N1, D)
+        ops.colsum_mul(Gc, m, pk.g(self.gamma2), M=B, N=D, ldx=N1 * D, ldy=D)
+        Dh = mlp.fc1.out_features
+        dH = new(B, Dh)
+        ops.gemm(gm, pk.w(mlp.fc2.weight), dH, b_kmajor=False, epilogue=EPI_DGELU, aux=pre, aux_deriv=T == torch.bfloat16)
+        ops.gemm(gm, hid, pk.g(mlp.fc2.weight), a_kmajor=False, b_kmajor=False)
+        ops.colsum(gm, pk.g(mlp.fc2.bias))
+        ops.gemm(dH, xcT, pk.g(mlp.fc1.weight), a_kmajor=False, b_kmajor=False)
+        ops.colsum(dH, pk.g(mlp.fc1.bias))
+        dx2c = dx2.view(B, N1 * D)[:, :D]
+        ops.gemm(dH, pk.w(mlp.fc1.weight), dx2c, b_kmajor=False, accumulate=True)          # dx2_c = G_c + the MLP's gradient
+        # norm2
+        g2w, gg2, gb2 = pk.f32(self.norm2.weight), pk.g(self.norm2.weight), pk.g(self.norm2.bias)
+        if self.tokens_norm:
+            dx1 = new(B, N1, D, dtype=f32)
+            ops.layernorm_bwd(dx2, x1, mean2, rstd2, g2w, None, dx1, None, gg2, gb2, M=M, D=D)
+        else:
+            dyc = ops.scale_cast(dx2c, new(B, D, dtype=f32), M=B, N=D, ldx=N1 * D)
+            ops.layernorm_bwd(dyc, x1, mean2, rstd2, g2w, None, dx2, None, gg2, gb2, M=B, D=D, x_stride=N1 * D,
+                              g_stride=N1 * D)                                            # over the CLS rows of dx2; dx1_p = dx2_p
+            dx1 = dx2
+        # the first residual's branch
+        da, dl = new(B, D), new(B, N1, D, dtype=f32)
+        ops.ca_merge_bwd(dx1, l, a, pk.f32(self.gamma1), da, dl, pk.g(self.gamma1), B, N1, D)
+        ops.gemm(da, o, pk.g(a_.proj.weight), a_kmajor=False, b_kmajor=False)
+        ops.colsum(da, pk.g(a_.proj.bias))
+        do = new(B, D)
+        ops.gemm(da, pk.w(a_.proj.weight), do, b_kmajor=False)
+        dq, dkv = new(B, D), new(M, 2 * D)
+        ops.class_attn_bwd(q, kv, kv[:, D:], 2 * D, do, psave, dq, dkv, dkv[:, D:], 2 * D, B, H, N1, hd, self.scale)
+        Wqkv, gW = pk.w(a_.qkv.weight), pk.g(a_.qkv.weight)
+        lc = l.view(B, N1 * D)[:, :D]
+        _gemm_dw(dkv, l, gW[D:], min_rows=256)                       # over all B*N1 rows: two levels in "fp32"
+        ops.gemm(dq, lc, gW[:D], a_kmajor=False, b_kmajor=False)
+        if a_.qkv.bias is not None:
+            gb = pk.g(a_.qkv.bias)
+            ops.colsum(dkv, gb[D:])
+            ops.colsum(dq, gb[:D])
+        dlm = dl.view(M, D)
+        ops.gemm(dkv, Wqkv[D:], dlm, b_kmajor=False, accumulate=True)
+        ops.gemm(dq, Wqkv[:D], dl.view(B, N1 * D)[:, :D], b_kmajor=False, accumulate=True)
+        # norm1 (its parameter gradients are needed whether or not dx is): dx = dx1 + LN1bwd(dl), in place over dx1
+        ops.layernorm_bwd(dlm, xa, mean1, rstd1, pk.f32(self.norm1.weight), dx1, dx1, None, pk.g(self.norm1.weight),
+                          pk.g(self.norm1.bias), M=M, D=D)
+        return dx1 if need_dx else None
