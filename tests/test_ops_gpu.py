@@ -1164,7 +1164,7 @@ def test_gemm_ragged_m_runs_on_the_tile_kernel_with_padded_rows(ops, layout, epi
         part = pbuf[:(M + 127) // 128]
         kw.update(epilogue=EPI_DGELU, aux=AUX, aux_deriv=True, colsum_part=part)
         want = want * side
-    assert ops.gemm_uses_fast(M, N, K, b_kmajor=bkm) or True
+    assert ops.gemm_uses_fast(M, N, K, b_kmajor=bkm, epilogue=kw.get("epilogue", EPI_STORE), launch_flags=LAUNCH_ROWS_PADDED)
     ops.gemm(A, Bm, C, **kw)
     torch.cuda.synchronize()
     assert_close(f"ragged {layout} {epi}", C, want, 1.2e-2)

@@ -244,8 +244,9 @@ def gemm_batched(A, B, C_out, *, M, N, K, lda, ldb, ldc, a_kmajor, b_kmajor, bat
 
 
 def gemm_uses_fast(M, N, K, *, a_kmajor=True, b_kmajor=True, in_dtype=BF16, c_dtype=BF16,
-                   epilogue=EPI_STORE, lda=None, ldb=None, ldc=None, colsum_part=False) -> bool:
-    """Host-only query (no GPU needed): would this problem take the fast kernel?"""
+                   epilogue=EPI_STORE, lda=None, ldb=None, ldc=None, colsum_part=False, launch_flags=0) -> bool:
+    """Host-only query (no GPU needed): would this problem take the fast kernel?  launch_flags: VITMI_LAUNCH_*, as the
+    call itself would pass them."""
     d = GemmDesc()
     d.M, d.N, d.K = M, N, K
     d.A = d.B = d.C = 256  # any non-null, 256-B aligned address
@@ -259,6 +260,7 @@ def gemm_uses_fast(M, N, K, *, a_kmajor=True, b_kmajor=True, in_dtype=BF16, c_dt
     d.in_dtype, d.c_dtype, d.r_dtype, d.epilogue = in_dtype, c_dtype, c_dtype, epilogue
     if colsum_part:
         d.colsum_part = 256
+    d.launch_flags = int(launch_flags)
     return bool(load().vitmi_gemm_uses_fast(C.byref(d)))
 
 
