@@ -15,12 +15,14 @@ the largest value measured on an MI355X (in brackets; every test prints its erro
   * The MFMA backward's fused qkv-bias sums are fp32 sums of the fp32 dQ / dK / dV accumulators, whose bf16-rounded
     P / dS operands leave errors that largely cancel over a column [8.4e-4].
 """
+import functools
+
 import pytest
 import torch
 import torch.nn.functional as F
 
-from swin_util import torch_window_attention
-from util import bf16_round, cosine, rel_err
+from swin_util import check, compare as _compare, dev_err, gen, inputs, nan, run, torch_window_attention, window_tokens
+from util import cosine, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -31,85 +33,15 @@ MFMA_OUT, MFMA_DQKV = 8e-3, 1e-2       # bf16 MFMA kernels
 QKV_BIAS = 1.5e-3                      # fused qkv-bias sums of the MFMA backward
 
 
-def gen(shape, seed, scale=1.0):
-    return torch.randn(shape, generator=torch.Generator("cpu").manual_seed(seed)) * scale
-
-
-def check(name, got, want, bound):
-    """rel-to-max error, printed beside its bound before it is asserted."""
-    g = got.detach().float().cpu()
-    assert tuple(g.shape) == tuple(want.shape), f"{name}: shape {tuple(g.shape)} vs {tuple(want.shape)}"
-    assert torch.isfinite(g).all(), f"{name}: non-finite values in result"
-    e = rel_err(got.detach().double().cpu(), want.double())
-    print(f"\n  {name}: {e:.2e} (bound {bound:.1e})", end="")
-    assert e <= bound, f"{name}: rel-to-max error {e:.3e} > {bound:.1e}"
-    return e
-
-
-def bounds(path):
-    """(out, lse, dqkv, dbias) bounds of a path: 'fp32', 'vector' (bf16) or 'mfma' (bf16)."""
-    return {"fp32": (FP32_GRADE, FP32_GRADE, FP32_GRADE, FP32_GRADE),
-            "vector": (VEC_OUT, FP32_GRADE, VEC_DQKV, FP32_GRADE),
-            "mfma": (MFMA_OUT, FP32_GRADE, MFMA_DQKV, FP32_GRADE)}[path]
+W7 = dict(FP32_GRADE=FP32_GRADE, VEC_OUT=VEC_OUT, VEC_DQKV=VEC_DQKV, MFMA_OUT=MFMA_OUT, MFMA_DQKV=MFMA_DQKV,
+          QKV_BIAS=QKV_BIAS)
+compare = functools.partial(_compare, W7)
 
 
 @pytest.fixture(scope="module")
 def ops(lib):
     from vit_torch_amd import ops as _o
     return _o
-
-
-def nan(shape, dt):
-    return torch.full(shape, float("nan"), device="cuda", dtype=dt)
-
-
-def inputs(B, Hh, Ww, ws, H, hd, seed):
-    """bf16-rounded qkv / dO (both sides see identical operands in both dtypes) and an fp32 bias table."""
-    C, N, L = H * hd, ws * ws, Hh * Ww
-    return (bf16_round(gen((B, L, 3 * C), seed)), bf16_round(gen((B, L, C), seed + 1)),
-            gen((H, N, N), seed + 2, 0.5))
-
-
-def run(ops, qkv, do, bias, mask, B, Hh, Ww, ws, shift, H, hd, dt, qkv_bias=False):
-    """forward + backward on the device, every output NaN-filled first; returns (O, lse, dqkv, dbias, dqkv_bias)."""
-    C, N, L = H * hd, ws * ws, Hh * Ww
-    Bw = B * (Hh // ws) * (Ww // ws)
-    Q = qkv.to("cuda", dt).contiguous()
-    O, lse = nan((B, L, C), dt), nan((Bw * H * N,), torch.float32)
-    bd = bias.cuda().float().contiguous()
-    md = mask.cuda().float().contiguous() if mask is not None else None
-    ops.win_attn_fwd(Q, O, lse, bd, md, Bw, H, N, hd, Hh, Ww, ws, shift, hd ** -0.5)
-    dqkv, dbias = nan((B, L, 3 * C), dt), nan((H * N * N,), torch.float32)
-    qb = nan((3 * C,), torch.float32) if qkv_bias else None
-    ops.win_attn_bwd(Q, do.to("cuda", dt).contiguous(), lse, bd, md, dqkv, dbias, Bw, H, N, hd, Hh, Ww, ws, shift,
-                     hd ** -0.5, dqkv_bias=qb)
-    return O, lse, dqkv, dbias.view(H, N, N), qb
-
-
-def compare(ops, lib, path, B, Hh, Ww, ws, shift, H, hd, seed, tag, images_per_chunk=None, force=True):
-    """One shape on one path against float64; returns (reference, dbias error, qkv-bias error or None).  `force`:
-    the vector path is forced through the MFMA switch (else left to the dispatch)."""
-    if path == "vector" and force:
-        lib.vitmi_debug_win_attn_mfma(0)
-    dt = torch.float32 if path == "fp32" else torch.bfloat16
-    qkv, do, bias = inputs(B, Hh, Ww, ws, H, hd, seed)
-    r = torch_window_attention(qkv, do, bias, B, Hh, Ww, ws, shift, H, hd, F64, images_per_chunk)
-    fuse = ops.win_attn_bwd_fuses_qkv_bias(torch.empty(1, dtype=dt), hd)
-    assert fuse == (path == "mfma" and hd == 32)
-    O, lse, dqkv, dbias, qb = run(ops, qkv, do, bias, r.mask, B, Hh, Ww, ws, shift, H, hd, dt, qkv_bias=fuse)
-    bo, bl, bq, bb = bounds(path)
-    check(f"{tag}.out", O, r.out, bo)
-    check(f"{tag}.lse", lse, r.lse, bl)
-    check(f"{tag}.dqkv", dqkv, r.dqkv, bq)
-    eb = check(f"{tag}.dbias", dbias, r.dbias, bb)
-    eq = None
-    if fuse:
-        eq = check(f"{tag}.dqkv_bias", qb, r.dqkv.reshape(-1, 3 * H * hd).sum(0), QKV_BIAS)
-        # the fused sums ride on the same kernel: dqkv is the same to the bit without them
-        _, _, dqkv2, _, _ = run(ops, qkv, do, bias, r.mask, B, Hh, Ww, ws, shift, H, hd, dt)
-        assert torch.equal(dqkv2.view(torch.int16) if dt == torch.bfloat16 else dqkv2,
-                           dqkv.view(torch.int16) if dt == torch.bfloat16 else dqkv)
-    return r, eb, eq
 
 
 # ------------------------------------------------------------------------------------------- 1. window sweep ---
@@ -178,22 +110,6 @@ def test_walk_against_float64(ops, lib, path, case):
 
 
 # ---------------------------------------------------------------------- 3. walks at Swin-T batch-256 stages ---
-def dev_err(got, want):
-    """rel-to-max error computed on the device (these tensors are hundreds of MB)."""
-    g, w = got.double(), want.double()
-    assert torch.isfinite(g).all()
-    return ((g - w).abs().max() / w.abs().max()).item()
-
-
-def window_tokens(Hh, Ww, ws, shift, bw, nW):
-    """token rows (in image order, over the whole batch) of window bw, through the roll."""
-    from oracle.swin_ref import window_partition
-    idx = torch.arange(Hh * Ww).view(1, Hh, Ww, 1)
-    if shift:
-        idx = torch.roll(idx, shifts=(-shift, -shift), dims=(1, 2))
-    return window_partition(idx, ws).view(nW, ws * ws)[bw % nW] + (bw // nW) * Hh * Ww
-
-
 # Swin-T (benchmark config C5, batch 256): (H, resolution, shift); stage 4 is one 7 x 7 window, so unshifted
 C5_STAGES = [(3, 56, 3), (6, 28, 3), (12, 14, 3), (24, 7, 0)]
 

@@ -901,6 +901,14 @@ __global__ __launch_bounds__(192) void win_attn_fwd_mfma144_kernel(const bf16* _
       st[kb][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[j], z, 0, 0, 0);
     }
   }
+  // The score tiles must have left the MFMA pipe before the softmax reads them.  The compiler counts those wait states
+  // itself, but not across the mask == nullptr branch it builds for the line below: in the <81> instance, where the
+  // dead tiles kb >= 6 drop out and tile (5, 2) is issued last and read first, that read came two instructions after
+  // its MFMA and saw the register's old value (window 9 without a mask: a wrong score of key 80 for queries 32..47 and
+  // 80; found by the float64 parity test).  So wait here, in the MFMAs' own block: 16 states cover the 8-pass MFMA.
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_nop 15" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
   const float* mwin = mask ? mask + (bw % geo.nW) * (int64_t)N * N : nullptr;
   float rinv[F144_QB];
 #pragma unroll
