@@ -336,11 +336,13 @@ def rpg(M):
 ALL_EPIS = (EPI_STORE, EPI_BIAS_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_PATCH_POS)
 LINEAR_EPIS = (EPI_STORE, EPI_RESIDUAL, EPI_DGELU, EPI_PATCH_POS)
 TAIL_CUS = 256
+# FastPlanKind (gemm_tile.h), as vitmi_debug_gemm_plan reports it; -1 = the call does not take the tile kernels
+PLAN_KINDS = {"WHOLE": 0, "SPLITK": 1, "TAIL_FINISHER": 2, "TAIL_FIXUP": 3, "TILE2_WHOLE": 4, "TILE2_SPLITK": 5}
 _PIPE_KS = (64, 128, 192, 256, 320)
 
 
 def tile_combo_built(layout, epi, c_bf16):
-    """Which (layout, epilogue, C dtype) the tile kernels instantiate (gemm_fast.hip combo_built)."""
+    """Which (layout, epilogue, C dtype) the tile kernels instantiate (gemm_tile.h dispatch_combo)."""
     if epi == EPI_STORE:
         return layout in ("nt", "nn", "tn")
     if epi == EPI_BIAS_GELU:

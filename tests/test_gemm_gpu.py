@@ -2,7 +2,9 @@
 float64 reference of tests/gemm_util.py.  Every case starts from vitmi_debug_reset and forces its own path; every operand,
 side input and output sits at a leading dimension larger than its row (row + 8 / row + 24) inside a NaN-filled buffer: an
 over-read of an input is a gross error, a store outside an output destroys a NaN canary, and an output element that is
-not written stays NaN.  The split-K / split-tail workspace is NaN-filled before every call.
+not written stays NaN.  The split-K / split-tail workspace is NaN-filled before every call.  Every tile case asks
+vitmi_debug_gemm_plan for the plan of its descriptor before the call and fails unless that is the path it is named after
+(off_plan).
 
 Paths (gemm_util.PATHS; shapes there):
   generic.bf16 / .fp32  impl = GENERIC: the 64x64 strided kernel, all four layouts
@@ -114,15 +116,43 @@ def dev(t, dt=F32):
 
 
 def gemm(ops, lib, A, B, C, **kw):
-    """ops.gemm with the workspace it will use NaN-filled first; returns (takes the tile kernels?, workspace bytes)."""
+    """ops.gemm with the workspace it will use NaN-filled first; returns (takes the tile kernels?, workspace bytes,
+    the plan (kind, pipe, deep, splits) the library follows for this call: vitmi_debug_gemm_plan)."""
     d = ops._gemm_desc(A, B, C, **kw)
     need = lib.vitmi_gemm_workspace(ctypes.byref(d))
     if need:
         ws = ops.workspace(need, A.device)
         ws[:ws.numel() // 4 * 4].view(F32).fill_(NAN)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()      # what ops.gemm passes
     fast = bool(lib.vitmi_gemm_uses_fast(ctypes.byref(d)))
+    out = [ctypes.c_int(-7) for _ in range(4)]
+    assert lib.vitmi_debug_gemm_plan(ctypes.byref(d), *map(ctypes.byref, out)) == 0
     ops.gemm(A, B, C, **kw)
-    return fast, need
+    return fast, need, tuple(o.value for o in out)
+
+
+def off_plan(path, v, K, epi, c_bf16, plan):
+    """Is the plan the path the case is named after?  None, or what is wrong.  (A forced main loop 3 exists only for
+    the fp32 residual: everything else resolves to loop 1.  The 256x128 tile splits the fp32 plain store from 16
+    64-deep k-steps on: min(256 / tiles, steps / 8) >= 2 slices at the one- and two-tile shapes here.)"""
+    kind, pipe, _, splits = plan
+    K_, P, v = U.PLAN_KINDS, U.PATHS[path], v or {}
+    name = {n: k for k, n in K_.items()}.get(kind, kind)
+    if path.startswith("t256") and kind not in (K_["WHOLE"], K_["SPLITK"], K_["TAIL_FINISHER"], K_["TAIL_FIXUP"]):
+        return f"plan {name}: not the 256x256 tile"
+    if path == "t256.splitk" and not (kind == K_["SPLITK"] and splits > 1):
+        return f"plan {name} with {splits} slices: the contraction is not split"
+    if path == "t256.tail" and kind != K_["TAIL_FIXUP" if v.get("fixup") else "TAIL_FINISHER"]:
+        return f"plan {name}: not the split tail asked for (fixup = {v.get('fixup')})"
+    if path == "t128":
+        split = epi == EPI_STORE and not c_bf16 and K // 64 >= 16
+        if kind != K_["TILE2_SPLITK" if split else "TILE2_WHOLE"] or (splits > 1) != split:
+            return f"plan {name} with {splits} slices at K = {K}"
+    if "pipe" in P:
+        want = P["pipe"] if P["pipe"] < 3 or (epi == EPI_RESIDUAL and not c_bf16) else 1
+        if pipe != want:
+            return f"main loop {pipe}, not {want}"
+    return None
 
 
 def _inputs(family, M, N, K, in_bf16, side_bf16, big):
@@ -156,6 +186,7 @@ class Run:
         akm, bkm = U.LAYOUTS[layout]
         in_dt, cdt = (BF if P["in_bf16"] else F32), (BF if c_bf16 else F32)
         self.M, self.N, self.cdt = M, N, cdt
+        self.path, self.K, self.epi, self.c_bf16 = path, K, epi, c_bf16
         self.Mp = Mp = (M + 255) // 256 * 256 if P.get("padded") else M
         e1, e2 = extras
         # (the padding rows of a rows-padded R / AUX hold 0.5: the kernel may read them, and whole tiles of numbers in C's
@@ -198,14 +229,19 @@ class Run:
             if "cls" in opts:
                 kw["cls"] = dev(x["cls"])
         self.C = C
-        self.fast, self.ws = gemm(ops, lib, A, B, C, **kw)
+        self.fast, self.ws, self.plan = gemm(ops, lib, A, B, C, **kw)
         torch.cuda.synchronize()
 
-    def problems(self, P):
-        """Structural failures: the path not taken, canaries destroyed, outputs not finite."""
+    def problems(self, P, v=None):
+        """Structural failures: the path not taken (under the switch settings v), canaries destroyed, outputs not finite."""
         out = []
         if (P["kind"] == "tile") != self.fast:
             out.append(f"vitmi_gemm_uses_fast = {self.fast}")
+        if (P["kind"] == "tile") != (self.plan[0] >= 0):
+            out.append(f"vitmi_debug_gemm_plan kind = {self.plan[0]}")
+        why = off_plan(self.path, v, self.K, self.epi, self.c_bf16, self.plan) if P["kind"] == "tile" else None
+        if why:
+            out.append(why)
         if P.get("needs_ws") and not self.ws:
             out.append("no workspace asked for: the contraction was not split")
         for nm, buf, cols in (("C", self.Cbuf, self.N), ("C2", self.C2buf, self.N)):
@@ -255,7 +291,7 @@ def test_exact_on_integers(ops, lib, path, epi):
     shape of the path, both extras of the leading dimensions in turn."""
     skip_unless_runnable(path)
     P = U.PATHS[path]
-    failures, n = [], 0
+    failures, n, kinds = [], 0, set()
     for v in variants(path):
         force(lib, path, v)
         for M, N, K, layout, e, c_bf16, opts in U.cases(path, "3.1"):
@@ -273,7 +309,7 @@ def test_exact_on_integers(ops, lib, path, epi):
                 why = U.integer_conditions(w, b)
                 assert why is None, f"{name} {nm}: {why}"
             r = Run(ops, lib, path, x, M, N, K, layout, epi, c_bf16, opts, extras=(8, 24) if n % 2 else (24, 8))
-            for p_ in r.problems(P):
+            for p_ in r.problems(P, v):
                 failures.append(f"{name}: {p_}")
             for nm, w, b in checks:
                 got = (r.C if nm == "C" else r.C2)
@@ -288,8 +324,11 @@ def test_exact_on_integers(ops, lib, path, epi):
                 m_ = mismatch(f"{name} colsum_part", r.part, want.colsum, F32)
                 if m_:
                     failures.append(m_)
+            kinds.add(r.plan[0])
     print(f"\n  {path} {U.EPI_NAMES[epi]}: {n} calls", end="")
     assert n > 0
+    if path == "t128" and epi == EPI_STORE:
+        assert U.PLAN_KINDS["TILE2_SPLITK"] in kinds and U.PLAN_KINDS["TILE2_WHOLE"] in kinds
     assert not failures, "\n".join(failures[:20]) + (f"\n... {len(failures)} in all" if len(failures) > 20 else "")
 
 
@@ -391,7 +430,7 @@ def test_accuracy_against_float64(ops, lib, path):
             want = U.reference(None, None, epilogue=epi, acc=x["acc"], **U.ref_kwargs(x, epi, opts))
             name = family + " " + opt_name(M, N, K, layout, epi, c_bf16, opts, v)
             r = Run(ops, lib, path, x, M, N, K, layout, epi, c_bf16, opts)
-            for p_ in r.problems(P):
+            for p_ in r.problems(P, v):
                 failures.append(f"{name}: {p_}")
             measure(name + " C", r.C, want.C, c_bf16, x["norm"], grade, failures)
             if want.C2 is not None:
@@ -454,14 +493,14 @@ def gelu_run(ops, lib, form, epi, deriv, depth, policy):
         _, A = U.place(a, 8, dt, "cuda")
         _, B = U.place(grid.t(), 24, dt, "cuda")
         C2buf, C2 = U.place(torch.full((M, N), NAN), 24, dt, "cuda", rows_alloc=Mp)
-        fast, _ = gemm(ops, lib, A, B, C, epilogue=epi, C2=C2, **kw)
+        fast, _, _ = gemm(ops, lib, A, B, C, epilogue=epi, C2=C2, **kw)
     else:
         a, b = torch.zeros((M, K)), torch.zeros((K, N))
         a[:, 0], b[0, :] = 1.0, 1.0
         _, A = U.place(a, 8, dt, "cuda")
         _, B = U.place(b, 24, dt, "cuda")
         _, AUX = U.place(arg, 24, dt, "cuda", rows_alloc=Mp, surplus=0.5)
-        fast, _ = gemm(ops, lib, A, B, C, b_kmajor=False, epilogue=epi, aux=AUX, **kw)
+        fast, _, _ = gemm(ops, lib, A, B, C, b_kmajor=False, epilogue=epi, aux=AUX, **kw)
     torch.cuda.synchronize()
     assert fast == tile
     assert U.canaries_intact(Cbuf, M, N, rows_alloc=Mp), "a store outside C"

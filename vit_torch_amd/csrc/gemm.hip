@@ -367,18 +367,47 @@ static bool small_lds_ok(const GemmArgs& g, int form) {
   return Kp * ry + (form == 2 ? 64 * rs : 0) <= 96 * 1024;
 }
 
+// which kernel family a call takes; `form`: the small / skinny kernel's form
+enum GemmPath { PATH_FAST, PATH_SMALL, PATH_SKINNY, PATH_GENERIC };
+static GemmPath choose_path(const vitmi_gemm_desc* d, const GemmArgs& g, int* form) {
+  const int in_bf16 = d->in_dtype == VITMI_BF16 ? 1 : 0;
+  const bool tuned = d->impl != VITMI_GEMM_GENERIC;
+  if (tuned && g.batch == 1 && gemm_fast_supported(g, in_bf16)) return PATH_FAST;
+  if (tuned || g_small_override == 1) {                             // batched form: one workgroup per small problem
+    *form = g_small_override == 0 ? -1 : gemm_small_form(g, in_bf16);
+    if (*form >= 0 && small_lds_ok(g, *form)) return PATH_SMALL;
+  }
+  if (tuned) {                                                      // the classifier head's fp32 products
+    *form = gemm_skinny_form(g, in_bf16);
+    if (*form >= 0) return PATH_SKINNY;
+  }
+  return PATH_GENERIC;
+}
+
 extern "C" int vitmi_gemm_uses_fast(const vitmi_gemm_desc* d) {
   GemmArgs g;
-  if (build_args(d, &g) != 0) return 0;
-  if (d->impl == VITMI_GEMM_GENERIC || g.batch > 1) return 0;
-  return gemm_fast_supported(g, d->in_dtype == VITMI_BF16) ? 1 : 0;
+  int form;
+  return build_args(d, &g) == 0 && choose_path(d, g, &form) == PATH_FAST ? 1 : 0;
 }
 
 extern "C" size_t vitmi_gemm_workspace(const vitmi_gemm_desc* d) {
   GemmArgs g;
-  if (build_args(d, &g) != 0 || d->impl == VITMI_GEMM_GENERIC) return 0;
-  if (g.batch > 1 || !gemm_fast_supported(g, d->in_dtype == VITMI_BF16)) return 0;
+  int form;
+  if (build_args(d, &g) != 0 || choose_path(d, g, &form) != PATH_FAST) return 0;
   return gemm_fast_workspace(g);
+}
+
+// diagnostic / test hook: the plan vitmi_gemm would follow for this descriptor, its workspace fields included.
+// kind: FastPlanKind (gemm_tile.h), or -1 when the call does not take the tile kernels (the other outputs are then 0)
+void gemm_fast_plan_query(const GemmArgs& g, int* kind, int* pipe, int* deep, int* splits);
+extern "C" int vitmi_debug_gemm_plan(const vitmi_gemm_desc* d, int* kind, int* pipe, int* deep, int* splits) {
+  GemmArgs g;
+  int form;
+  if (int rc = build_args(d, &g)) return rc;
+  VITMI_REQUIRE(kind && pipe && deep && splits, VITMI_E_BADARG, "gemm_plan: null output");
+  *kind = -1; *pipe = *deep = *splits = 0;
+  if (choose_path(d, g, &form) == PATH_FAST) gemm_fast_plan_query(g, kind, pipe, deep, splits);
+  return 0;
 }
 
 size_t gemm_fast_pair_workspace(const GemmArgs& a, const GemmArgs& b);
@@ -414,23 +443,17 @@ extern "C" int vitmi_gemm(const vitmi_gemm_desc* d, void* stream_) {
   int rc = build_args(d, &g);
   if (rc) return rc;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const bool in_bf16 = d->in_dtype == VITMI_BF16;
-  const bool fast_ok = g.batch == 1 && gemm_fast_supported(g, in_bf16);
+  int form = -1;
+  const GemmPath path = choose_path(d, g, &form);
   if (d->impl == VITMI_GEMM_FAST)
-    VITMI_REQUIRE(fast_ok, VITMI_E_SHAPE, "gemm: VITMI_GEMM_FAST requested but shape/dtype/alignment unsupported (M=%lld N=%lld K=%lld)",
+    VITMI_REQUIRE(path == PATH_FAST, VITMI_E_SHAPE, "gemm: VITMI_GEMM_FAST requested but shape/dtype/alignment unsupported (M=%lld N=%lld K=%lld)",
                   (long long)d->M, (long long)d->N, (long long)d->K);
-  if (fast_ok && d->impl != VITMI_GEMM_GENERIC) return gemm_fast_launch(g, stream);
+  if (path == PATH_FAST) return gemm_fast_launch(g, stream);
   VITMI_REQUIRE(!d->colsum_part, VITMI_E_BADARG,
                 "gemm: colsum_part is produced only by the aligned bf16 path with EPI_DGELU (ask vitmi_gemm_uses_fast)");
-
-  if (d->impl != VITMI_GEMM_GENERIC || g_small_override == 1) {     // batched form: one workgroup per small problem
-    const int form = g_small_override == 0 ? -1 : gemm_small_form(g, in_bf16 ? 1 : 0);
-    if (form >= 0 && small_lds_ok(g, form)) return gemm_small_launch(g, form, stream);
-  }
-  if (d->impl != VITMI_GEMM_GENERIC) {                              // the classifier head's fp32 products
-    const int sform = gemm_skinny_form(g, in_bf16 ? 1 : 0);
-    if (sform >= 0) return gemm_skinny_launch(g, sform, stream);
-  }
+  if (path == PATH_SMALL) return gemm_small_launch(g, form, stream);
+  if (path == PATH_SKINNY) return gemm_skinny_launch(g, form, stream);
+  const bool in_bf16 = d->in_dtype == VITMI_BF16;
   dim3 grid((unsigned)((g.N + GBN - 1) / GBN), (unsigned)((g.M + GBM - 1) / GBM), (unsigned)g.batch);
   VITMI_REQUIRE(grid.y <= 65535u, VITMI_E_SHAPE, "gemm: M too large for the generic kernel grid");
   if (in_bf16) hipLaunchKernelGGL(gemm_generic_kernel<bf16>, grid, dim3(256), 0, stream, g);

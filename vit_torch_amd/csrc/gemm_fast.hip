@@ -694,17 +694,11 @@ __global__ __launch_bounds__(NTHREADS) void gemm_fast_kernel(GemmArgs g, int til
       raw_barrier();
       if (dbg) { t0 = stamp(); tWR += t0 - t1; }
       // ---- M(j)
-#ifdef VITMI_GEMM_SETPRIO
-      __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
       for (int mi = 0; mi < 8; ++mi)
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni)
           acc[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[ni], af[mi], acc[ni][mi], 0, 0, 0);
-#ifdef VITMI_GEMM_SETPRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
       if (grp == 0) { if constexpr (STEADY) wait_vm_c<4 * (AHEAD - 1)>(); else wait_vm(nvm); }
       if (dbg) { t1 = stamp(); tM += t1 - t0; }
       if (STEADY || !(grp == 1 && j == ns - 1)) raw_barrier();
@@ -1085,18 +1079,14 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int splits, E
   }
 }
 
-// split-K plan for a problem with `tiles` output tiles and `nt` k-steps
+// split-K of the 256x256 tile: problems of up to 128 tiles, cut for g_splitk_target workgroups (splitk_plan, gemm_tile.h)
 static std::atomic<int> g_splitk_target{256};
-inline void splitk_plan(int tiles, int nt, int* splits, int* ksps) {
-  int s = 1;
-  if (tiles <= 128 && nt >= 16) {
-    s = g_splitk_target / tiles;
-    if (s > nt / 8) s = nt / 8;
-    if (s < 1) s = 1;
-  }
-  const int k = (nt + s - 1) / s;
-  *ksps = k;
-  *splits = (nt + k - 1) / k;
+constexpr int SPLITK_MAX_TILES = 128;
+static int launch_splitk_reduce(const float* ws, int splits, const EpiArgs& e, int64_t M, int64_t N, hipStream_t stream, const char* what) {
+  int64_t blocks = (M * N / 4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ws, splits, e, M, N);
+  return vitmi_check_launch(what);
 }
 
 // Tail tiles: C = epilogue(sum of the k-slices).  16 blocks of 256 threads per 256x256 tile:
@@ -1139,7 +1129,7 @@ static std::atomic<int> g_tail_override{-1};
 // diagnostic / test hook: 0 = never split the tail, 1 = whenever the shape allows, -1 = default heuristic
 extern "C" void vitmi_debug_gemm_tail(int mode) { g_tail_override = mode; }
 constexpr int TAIL_SPLITS = 3;
-// tail_plan: is the remainder round worth slicing?  Needs a workspace of TAIL_SPLITS full
+// tail_plan_shape: is the remainder round worth slicing?  Needs a workspace of TAIL_SPLITS full
 // M x N fp32 slabs (only the tail tiles' part is touched), no fused column sums, and a
 // contraction long enough that a third of it still amortises the partial-tile traffic.
 static bool tail_plan_shape(const GemmArgs& g, int nwg, int* rem, int* splits, int* ksps, bool forced) {
@@ -1157,11 +1147,6 @@ static bool tail_plan_shape(const GemmArgs& g, int nwg, int* rem, int* splits, i
 }
 // workspace of a split tail: the slices' partial slabs + one arrival counter per tile (rounded up to 4 KiB)
 static size_t tail_ws_bytes(const GemmArgs& g) { return (size_t)TAIL_SPLITS * g.M * g.N * sizeof(float) + 4096; }
-static bool tail_plan(const GemmArgs& g, int nwg, int* rem, int* splits, int* ksps) {
-  if (g_tail_override == 0 || g.e.colsum_part || g.e.accumulate || (g.M % BM) != 0) return false;   // (the slices' workspace is M x N)
-  if (!tail_plan_shape(g, nwg, rem, splits, ksps, g_tail_override == 1)) return false;
-  return g.ws != nullptr && g.ws_bytes >= tail_ws_bytes(g) && *rem <= NTHREADS;
-}
 // 0 (default) = row-wise finisher kernel after the slices (all 256 CUs sum the 79 tiles' slabs: 60 MB in 12-15 us);
 // 1 = the last slice of a tile to arrive applies the epilogue itself (FIX).  The in-kernel form was asked for by VERDICT r02
 // (item 1a), is built and tested (bit-identical results), and measured SLOWER inside the ViT-B/16 step, one box, interleaved:
@@ -1194,37 +1179,6 @@ static int pipe_mode() {   // -1 = automatic (per layout), else forced 0/1/2
   return mode;
 }
 
-template <bool A_KM, bool B_KM, int MODE, typename TC, int PIPE>
-int launch_p(const GemmArgs& g, hipStream_t stream);
-
-template <bool A_KM, bool B_KM, int MODE, typename TC>
-int launch(const GemmArgs& g, hipStream_t stream) {
-  int pm = pipe_mode();
-  constexpr bool CAN_FOLD = MODE == VITMI_EPI_RESIDUAL && sizeof(TC) == 4;
-  if (pm < 0) {
-    pm = (A_KM && B_KM) ? 2 : 1;   // k-major operands want full-line DMA (PIPE 2)
-    // the plain-store forward with a short contraction (qkv: K = 768) runs best on the simple two-stage
-    // loop: 189 -> 175 us inside the ViT-B/16 step (A/B of the three loops in one process); with an
-    // epilogue that reads or computes (GELU, residual) or K = 3072 the phased loops win
-    // (round 3: with the k-half unrolled and the DMAs in the SGPR-base form the phased loop wins here too —
-    // 160-166 us against 169-171 for the qkv forward, one process — so nothing selects the two-stage loop by default)
-    // the fp32-stream residual epilogue takes the ring-of-three loop that streams R through LDS
-    if (CAN_FOLD && g_rfold_override != 0 && !g.e.gamma && !g.e.rowscale && !g.e.C2 && !g.e.r_bf16 && g.K >= 640) pm = 3;
-  }
-  if (pm == 0) return launch_p<A_KM, B_KM, MODE, TC, 0>(g, stream);
-  if (pm == 1) return launch_p<A_KM, B_KM, MODE, TC, 1>(g, stream);
-  if constexpr (CAN_FOLD) { if (pm == 3) return launch_p<A_KM, B_KM, MODE, TC, 3>(g, stream); }
-  else if (pm == 3) pm = 1;        // PIPE 3 exists only where the fold does: everything else keeps the ring of four
-  if (pm == 1) return launch_p<A_KM, B_KM, MODE, TC, 1>(g, stream);
-  return launch_p<A_KM, B_KM, MODE, TC, 2>(g, stream);
-}
-
-// split-K: two stages (strips alias them after the loop); persistent launches: stages + 32 KiB of
-// strips above them = the CU's 160 KiB (PIPE 3: ring of three + residual strips, the same size)
-template <int MODE, typename TC, bool SPLITK, int PIPE>
-constexpr int lds_bytes() {
-  return SPLITK ? 2 * STAGE_BYTES : RF_LDS;
-}
 // launch_flags & VITMI_LAUNCH_SHARED_DEVICE: one tile per workgroup (grid = tiles); else the persistent grid
 static int persistent_grid(int nwg, int launch_flags) {
   if (!vitmi_persist_on(launch_flags)) return nwg;
@@ -1266,119 +1220,96 @@ static int band_for(const GemmArgs& g, int tiles_m, int tiles_n) {
   return band;
 }
 
+// ---- the kernel a plan names.  Instantiations, per (layout, MODE, TC) and main loop PIPE (3 only with the fp32 residual):
+//   main launch      <.., MODE, TC, false, PIPE, false, DEEP>: DEEP 1 for the bf16 RESIDUAL / DGELU, DEEP 2 for every bf16
+//                    epilogue but PATCH_POS
+//   raw k-slices     <.., EPI_STORE, float, true, PIPE>: split-K, and the tail slices a finisher kernel sums (STORE / RESIDUAL)
+//   fix-up k-slices  <.., MODE, TC, true, PIPE, true> (STORE / RESIDUAL)
+// nullptr: not built (plan_fast never asks for it).
+using FastKernel = void (*)(GemmArgs, int, int, int, int, float*, int);
 template <bool A_KM, bool B_KM, int MODE, typename TC, int PIPE>
-int launch_p(const GemmArgs& g_in, hipStream_t stream) {
-  GemmArgs g = g_in;
-  g.rfold = g_rfold_override == 0 ? 0 : 1;
-  const int tiles_m = (int)((g.M + BM - 1) / BM), tiles_n = (int)(g.N / BN);      // ragged M: see ragged_m_ok
-  const int nwg = tiles_m * tiles_n;
-  g.band = band_for(g, tiles_m, tiles_n);
-  {   // tile time estimate in shader cycles: ~3.6 k per 64-deep k-step + an epilogue
-    const int64_t est = (g.K / BK) * 3600 + 8000;
-    g.stag_cycles = (int)(est * g_stagger_permille / 1000);
-    g.stag_phases = g_stagger_phases;
-  }
-  if constexpr (MODE == VITMI_EPI_STORE && sizeof(TC) == 4) {
-    int splits, ksps;
-    splitk_plan(nwg, (int)(g.K / BK), &splits, &ksps);
-    // (a ragged last row tile stores WHOLE 256-row tiles: with the slices strided by M rows its padding rows would land on
-    // the first rows of the next slice and, for the last slice, beyond the workspace — ragged M never splits K)
-    if (splits > 1 && (g.M % BM) == 0 && g.ws && g.ws_bytes >= (size_t)splits * g.M * g.N * sizeof(float)) {
-      auto kern = gemm_fast_kernel<A_KM, B_KM, MODE, TC, true, PIPE>;
-      if (int rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(kern), 2 * STAGE_BYTES, "gemm_fast(split-K)")) return rc;
-      float* ws = reinterpret_cast<float*>(g.ws);
-      hipLaunchKernelGGL(kern, dim3(nwg * splits), dim3(NTHREADS), 2 * STAGE_BYTES, stream, g, tiles_n, nwg * splits, nwg, ksps, ws, 0);
-      int rc = vitmi_check_launch("gemm_fast_kernel(split-K)");
-      if (rc) return rc;
-      const int64_t work = g.M * g.N / 4;
-      int64_t blocks = (work + 255) / 256;
-      if (blocks > 2048) blocks = 2048;
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ws, splits, g.e, g.M, g.N);
-      return vitmi_check_launch("splitk_reduce_kernel");
+FastKernel pick_kernel_p(bool splitk, bool fix, int deep) {
+  constexpr bool SLICED = MODE == VITMI_EPI_STORE || MODE == VITMI_EPI_RESIDUAL;
+  constexpr bool CAN_DEEP = sizeof(TC) == 2 && (MODE == VITMI_EPI_RESIDUAL || MODE == VITMI_EPI_DGELU);
+  if (splitk) {
+    if constexpr (SLICED) {
+      if (fix) return gemm_fast_kernel<A_KM, B_KM, MODE, TC, true, PIPE, true>;
+      return gemm_fast_kernel<A_KM, B_KM, VITMI_EPI_STORE, float, true, PIPE>;
     }
+    return nullptr;
   }
-  // ---- split tail: a launch of q full rounds plus a short remainder leaves most CUs idle
-  // for a whole tile time.  The remainder tiles are instead contracted in TAIL_SPLITS k-slices
-  // (one short round on all CUs, raw fp32 partial tiles to the workspace) and finished by a
-  // row-wise kernel that sums the slices in a fixed order and applies the epilogue.
-  if constexpr (MODE == VITMI_EPI_STORE || MODE == VITMI_EPI_RESIDUAL) {
-    int rem = 0, splits = 0, ksps = 0;
-    if (tail_plan(g, nwg, &rem, &splits, &ksps)) {
-      const int full = nwg - rem;
-      constexpr bool CAN_DEEP = sizeof(TC) == 2 && (MODE == VITMI_EPI_RESIDUAL || MODE == VITMI_EPI_DGELU);
-      auto kmain = gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE>;
-      if constexpr (MODE == VITMI_EPI_STORE && sizeof(TC) == 2) {
-        if (g.side_depth >= 3 && g.e.alpha == 1.f && !g.e.accumulate && g.e.c_policy == 2) kmain = gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE, false, 2>;
-      }
-      if constexpr (CAN_DEEP) {
-        if (g.side_depth >= 3) {
-          kmain = gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE, false, 1>;
-          if constexpr (MODE == VITMI_EPI_RESIDUAL) {
-            if (!g.e.C2 && !g.e.rowscale && g.e.c_policy == 0) kmain = gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE, false, 2>;
-          } else {
-            if (g.e.aux_deriv && g.e.c_policy == 2) kmain = gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE, false, 2>;
-          }
-        }
-      }
-      constexpr int LDSM = lds_bytes<MODE, TC, false, PIPE>();
-      if (int rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(kmain), LDSM, "gemm_fast")) return rc;
-      float* ws = reinterpret_cast<float*>(g.ws);
-      unsigned* cnt = reinterpret_cast<unsigned*>(ws + (size_t)TAIL_SPLITS * g.M * g.N);
-      if (g_tail_fixup) {
-        // the last slice of a tile to arrive applies the epilogue itself (FIX): two launches instead of three
-        auto ktail = gemm_fast_kernel<A_KM, B_KM, MODE, TC, true, PIPE, true>;
-        if (int rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(ktail), 2 * STAGE_BYTES, "gemm_fast(tail)")) return rc;
-        GemmArgs gm = g, gt = g;
-        gm.zero_cnt = cnt; gm.zero_n = rem;
-        gt.fix_cnt = cnt;
-        hipLaunchKernelGGL(kmain, dim3(persistent_grid(full, g.launch_flags)), dim3(NTHREADS), LDSM, stream, gm, tiles_n, full, full, 0, (float*)nullptr, 0);
-        int rc = vitmi_check_launch("gemm_fast_kernel(full rounds)");
-        if (rc) return rc;
-        hipLaunchKernelGGL(ktail, dim3(rem * splits), dim3(NTHREADS), 2 * STAGE_BYTES, stream, gt, tiles_n, rem * splits, rem, ksps, ws, full);
-        return vitmi_check_launch("gemm_fast_kernel(tail slices + fix-up)");
-      }
-      auto ktail = gemm_fast_kernel<A_KM, B_KM, VITMI_EPI_STORE, float, true, PIPE>;
-      if (int rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(ktail), 2 * STAGE_BYTES, "gemm_fast(tail)")) return rc;
-      hipLaunchKernelGGL(kmain, dim3(persistent_grid(full, g.launch_flags)), dim3(NTHREADS), LDSM, stream, g, tiles_n, full, full, 0, (float*)nullptr, 0);
-      int rc = vitmi_check_launch("gemm_fast_kernel(full rounds)");
-      if (rc) return rc;
-      hipLaunchKernelGGL(ktail, dim3(rem * splits), dim3(NTHREADS), 2 * STAGE_BYTES, stream, g, tiles_n, rem * splits, rem, ksps, ws, full);
-      if ((rc = vitmi_check_launch("gemm_fast_kernel(tail slices)"))) return rc;
-      hipLaunchKernelGGL((tail_epilogue_kernel<MODE, TC>), dim3(rem * 16), dim3(256), 0, stream, ws, splits, g.e, g.M, g.N, tiles_n, full, g.band);
-      return vitmi_check_launch("tail_epilogue_kernel");
-    }
-  }
-  constexpr bool CAN_DEEP2 = sizeof(TC) == 2 && (MODE == VITMI_EPI_RESIDUAL || MODE == VITMI_EPI_DGELU);
-  auto kern = gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE>;
-  if constexpr (MODE == VITMI_EPI_BIAS_GELU && sizeof(TC) == 2) {
-    if (g.side_depth >= 3 && g.e.aux_deriv && g.e.C2 && g.e.c_policy == 2) kern = gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE, false, 2>;
-  }
-  if constexpr (MODE == VITMI_EPI_STORE && sizeof(TC) == 2) {
-    if (g.side_depth >= 3 && g.e.alpha == 1.f && !g.e.accumulate && g.e.c_policy == 2) kern = gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE, false, 2>;
-  }
-  if constexpr (CAN_DEEP2) {
-    if (g.side_depth >= 3) {
-      kern = gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE, false, 1>;
-      if constexpr (MODE == VITMI_EPI_RESIDUAL) {
-        if (!g.e.C2 && !g.e.rowscale && g.e.c_policy == 0) kern = gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE, false, 2>;
-      } else {
-        if (g.e.aux_deriv && g.e.c_policy == 2) kern = gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE, false, 2>;
-      }
-    }
-  }
-  constexpr int LDSK = lds_bytes<MODE, TC, false, PIPE>();
-  if (int rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(kern), LDSK, "gemm_fast")) return rc;
-  hipLaunchKernelGGL(kern, dim3(persistent_grid(nwg, g.launch_flags)), dim3(NTHREADS), LDSK, stream, g, tiles_n, nwg, nwg, 0, (float*)nullptr, 0);
-  return vitmi_check_launch("gemm_fast_kernel");
+  if constexpr (CAN_DEEP) { if (deep == 1) return gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE, false, 1>; }
+  if constexpr (sizeof(TC) == 2 && MODE != VITMI_EPI_PATCH_POS) { if (deep == 2) return gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE, false, 2>; }
+  return deep == 0 ? gemm_fast_kernel<A_KM, B_KM, MODE, TC, false, PIPE> : nullptr;
 }
+template <bool A_KM, bool B_KM, int MODE, typename TC>
+FastKernel pick_kernel(int pipe, bool splitk, bool fix, int deep) {
+  if (pipe == 0) return pick_kernel_p<A_KM, B_KM, MODE, TC, 0>(splitk, fix, deep);
+  if (pipe == 1) return pick_kernel_p<A_KM, B_KM, MODE, TC, 1>(splitk, fix, deep);
+  if (pipe == 2) return pick_kernel_p<A_KM, B_KM, MODE, TC, 2>(splitk, fix, deep);
+  if constexpr (MODE == VITMI_EPI_RESIDUAL && sizeof(TC) == 4) { if (pipe == 3) return pick_kernel_p<A_KM, B_KM, MODE, TC, 3>(splitk, fix, deep); }
+  return nullptr;
+}
+
+// one gemm_fast_kernel launch.  LDS: k-slices take two stages (strips alias them after the loop); persistent launches
+// stages + 32 KiB of strips above them = the CU's 160 KiB (PIPE 3: ring of three + residual strips, the same size)
+static int launch_tiles(FastKernel kern, bool splitk, int grid, const GemmArgs& g, int tiles_n, int nwg, int ntiles, int ksps,
+                        float* ws, int tile0, hipStream_t stream, const char* what) {
+  if (!kern) return vitmi_fail(VITMI_E_SHAPE, "%s: kernel variant not built", what);
+  const int lds = splitk ? 2 * STAGE_BYTES : RF_LDS;
+  if (int rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(kern), lds, what)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHREADS), lds, stream, g, tiles_n, nwg, ntiles, ksps, ws, tile0);
+  return vitmi_check_launch(what);
+}
+
+// issue what the plan says: the main launch, then the tail slices and their finisher, or the split-K reduce.
+// Split tail: a launch of q full rounds plus a short remainder leaves most CUs idle for a whole tile time.  The
+// remainder tiles are instead contracted in TAIL_SPLITS k-slices (one short round on all CUs, raw fp32 partial tiles
+// to the workspace) and finished by a row-wise kernel that sums the slices in a fixed order and applies the epilogue.
+template <bool A_KM, bool B_KM, int MODE, typename TC>
+int issue(const GemmArgs& g_in, const FastPlan& p, hipStream_t stream) {
+  GemmArgs g = g_in;
+  g.rfold = p.rfold; g.band = p.band; g.stag_cycles = p.stag_cycles; g.stag_phases = p.stag_phases;
+  const int tiles_n = (int)(g.N / BN);
+  const int nwg = (int)((g.M + BM - 1) / BM) * tiles_n;      // ragged M: see ragged_m_ok
+  float* ws = reinterpret_cast<float*>(g.ws);
+  if (p.kind == PLAN_SPLITK) {
+    if (int rc = launch_tiles(pick_kernel<A_KM, B_KM, MODE, TC>(p.pipe, true, false, 0), true, nwg * p.splits, g, tiles_n,
+                              nwg * p.splits, nwg, p.ksps, ws, 0, stream, "gemm_fast_kernel(split-K)")) return rc;
+    return launch_splitk_reduce(ws, p.splits, g.e, g.M, g.N, stream, "splitk_reduce_kernel");
+  }
+  const bool tail = p.kind == PLAN_TAIL_FINISHER || p.kind == PLAN_TAIL_FIXUP, fix = p.kind == PLAN_TAIL_FIXUP;
+  const int full = tail ? nwg - p.rem : nwg;
+  unsigned* cnt = fix ? reinterpret_cast<unsigned*>(ws + (size_t)TAIL_SPLITS * g.M * g.N) : nullptr;      // arrival counters
+  GemmArgs gm = g;
+  if (fix) { gm.zero_cnt = cnt; gm.zero_n = p.rem; }
+  if (int rc = launch_tiles(pick_kernel<A_KM, B_KM, MODE, TC>(p.pipe, false, false, p.deep), false, persistent_grid(full, g.launch_flags), gm,
+                            tiles_n, full, full, 0, nullptr, 0, stream, tail ? "gemm_fast_kernel(full rounds)" : "gemm_fast_kernel")) return rc;
+  if (!tail) return 0;
+  GemmArgs gt = g;
+  if (fix) gt.fix_cnt = cnt;
+  if (int rc = launch_tiles(pick_kernel<A_KM, B_KM, MODE, TC>(p.pipe, true, fix, 0), true, p.rem * p.splits, gt, tiles_n,
+                            p.rem * p.splits, p.rem, p.ksps, ws, full, stream, fix ? "gemm_fast_kernel(tail slices + fix-up)" : "gemm_fast_kernel(tail slices)")) return rc;
+  if (fix) return 0;
+  if constexpr (MODE == VITMI_EPI_STORE || MODE == VITMI_EPI_RESIDUAL) {
+    hipLaunchKernelGGL((tail_epilogue_kernel<MODE, TC>), dim3(p.rem * 16), dim3(256), 0, stream, ws, p.splits, g.e, g.M, g.N, tiles_n, full, g.band);
+    return vitmi_check_launch("tail_epilogue_kernel");
+  }
+  return vitmi_fail(VITMI_E_SHAPE, "gemm_fast: no split tail for this epilogue");
+}
+struct IssueFast {      // dispatch_combo functor
+  const GemmArgs& g; const FastPlan& p; hipStream_t s; int rc;
+  template <bool A_KM, bool B_KM, int MODE, typename TC> void operator()() { rc = issue<A_KM, B_KM, MODE, TC>(g, p, s); }
+};
+struct ComboOnly { template <bool, bool, int, typename> void operator()() const {} };
 
 enum { OUT_BF16 = 0, OUT_F32 = 1 };
 
 }  // namespace
 
 bool gemm_fast2_shape_ok(const GemmArgs& g);
-size_t gemm_fast2_workspace(const GemmArgs& g);
-int gemm_fast2_launch(const GemmArgs& g, hipStream_t s);
+FastPlan gemm_fast2_plan(const GemmArgs& g, size_t ws_avail);
+int gemm_fast2_launch(const GemmArgs& g, const FastPlan& p, hipStream_t s);
 
 // diagnostic hook: workgroups a split-K launch of the 256x256 kernel aims at (default 256)
 extern "C" void vitmi_debug_gemm_splitk_target(int n) { g_splitk_target = n > 0 ? n : 256; }
@@ -1413,26 +1344,12 @@ static bool use_tile2(const GemmArgs& g) {
   return tile_mode() == 2 || (g.M % BM) != 0 || (g.N % BN) != 0 || (g.K % BK) != 0;
 }
 
-// which (layout, epilogue, output dtype) combinations are instantiated
-static bool combo_built(const GemmArgs& g) {
-  const EpiArgs& e = g.e;
-  const bool nt = g.a_km && g.b_km, nn = g.a_km && !g.b_km, tn = !g.a_km && !g.b_km;
-  switch (e.mode) {
-    case VITMI_EPI_STORE: return (nt || nn || tn);
-    case VITMI_EPI_BIAS_GELU: return nt && e.c_bf16;
-    case VITMI_EPI_RESIDUAL: return nt;
-    case VITMI_EPI_DGELU: return nn && e.c_bf16;
-    case VITMI_EPI_PATCH_POS: return nt;
-  }
-  return false;
-}
-
 bool gemm_fast_supported(const GemmArgs& g, int in_bf16) {
   if (!in_bf16) return false;
   if (!use_tile2(g) && ((g.M % BM && !ragged_m_ok(g)) || g.N % BN || g.K % BK)) return false;
   if (g.e.colsum_part && (g.e.mode != VITMI_EPI_DGELU || !is_aligned(g.e.colsum_part, 16))) return false;
   if ((g.M + BM - 1) / BM * (g.N / BN) > (1 << 30)) return false;
-  if (!combo_built(g)) return false;
+  if (!dispatch_combo(g, ComboOnly{})) return false;      // (layout, epilogue, output dtype) not instantiated
   const EpiArgs& e = g.e;
   if (g.lda % 8 || g.ldb % 8 || !is_aligned(g.A, 16) || !is_aligned(g.B, 16)) return false;
   const size_t cb = e.c_bf16 ? 8 : 16;
@@ -1447,39 +1364,77 @@ bool gemm_fast_supported(const GemmArgs& g, int in_bf16) {
   return true;
 }
 
-size_t gemm_fast_workspace(const GemmArgs& g) {
-  if (use_tile2(g)) return gemm_fast2_workspace(g);
-  const int tiles = (int)((g.M + BM - 1) / BM * (g.N / BN));
-  size_t need = 0;
-  if (g.e.mode == VITMI_EPI_STORE && !g.e.c_bf16 && (g.M % BM) == 0) {
+// The one place that decides what a supported problem launches; `ws_avail` = bytes of 16-B-aligned workspace the
+// caller holds (SIZE_MAX: "what would you like", the workspace query).  Precedence: split-K, then the split tail,
+// each only if the workspace suffices, else the whole launch.  Does not allocate: it runs on every eager launch.
+FastPlan plan_fast(const GemmArgs& g, size_t ws_avail) {
+  if (use_tile2(g)) return gemm_fast2_plan(g, ws_avail);
+  const EpiArgs& e = g.e;
+  const bool c16 = e.c_bf16 != 0, whole_m = (g.M % BM) == 0;
+  const int tiles_m = (int)((g.M + BM - 1) / BM), tiles_n = (int)(g.N / BN);      // ragged M: see ragged_m_ok
+  const int nwg = tiles_m * tiles_n, nt = (int)(g.K / BK);
+  FastPlan p = {};
+  p.kind = PLAN_WHOLE;
+  p.splits = 1; p.ksps = nt;
+  // ---- main loop.  Automatic: k-major operands want full-line DMA (PIPE 2), the others the ring of four (PIPE 1); the
+  // fp32-stream residual epilogue takes the ring-of-three loop that streams R through LDS (PIPE 3).  Nothing selects the
+  // two-stage loop (PIPE 0) by default: with the k-half unrolled and the DMAs in the SGPR-base form the phased loops win
+  // on the short plain-store forward too (qkv, K = 768: 160-166 us against 169-171, one process).
+  const bool can_fold = e.mode == VITMI_EPI_RESIDUAL && !c16;
+  p.pipe = pipe_mode();
+  if (p.pipe < 0) {
+    p.pipe = (g.a_km && g.b_km) ? 2 : 1;
+    if (can_fold && g_rfold_override != 0 && !e.gamma && !e.rowscale && !e.C2 && !e.r_bf16 && g.K >= 640) p.pipe = 3;
+  }
+  if (p.pipe == 3 && !can_fold) p.pipe = 1;      // PIPE 3 exists only where the fold does: everything else keeps the ring of four
+  if (p.pipe > 3) p.pipe = 2;
+  p.rfold = g_rfold_override == 0 ? 0 : 1;
+  p.band = band_for(g, tiles_m, tiles_n);
+  // start stagger from a tile time estimate in shader cycles: ~3.6 k per 64-deep k-step + an epilogue
+  p.stag_cycles = (int)(((int64_t)nt * 3600 + 8000) * g_stagger_permille / 1000);
+  p.stag_phases = g_stagger_phases;
+  // ---- epilogue depth of the main kernel (bf16 outputs): side inputs three strips ahead (1), straight-line form (2)
+  if (c16 && g.side_depth >= 3) {
+    if (e.mode == VITMI_EPI_BIAS_GELU) p.deep = (e.aux_deriv && e.C2 && e.c_policy == 2) ? 2 : 0;
+    if (e.mode == VITMI_EPI_STORE) p.deep = (e.alpha == 1.f && !e.accumulate && e.c_policy == 2) ? 2 : 0;
+    if (e.mode == VITMI_EPI_RESIDUAL) p.deep = (!e.C2 && !e.rowscale && e.c_policy == 0) ? 2 : 1;
+    if (e.mode == VITMI_EPI_DGELU) p.deep = (e.aux_deriv && e.c_policy == 2) ? 2 : 1;
+  }
+  // ---- split-K (fp32 plain store).  A ragged last row tile stores WHOLE 256-row tiles: with the slices strided by M rows
+  // its padding rows would land on the first rows of the next slice and, for the last slice, beyond the workspace
+  if (e.mode == VITMI_EPI_STORE && !c16 && whole_m) {
     int splits, ksps;
-    splitk_plan(tiles, (int)(g.K / BK), &splits, &ksps);
-    if (splits > 1) need = (size_t)splits * g.M * g.N * sizeof(float);
+    splitk_plan(nwg, nt, SPLITK_MAX_TILES, g_splitk_target, &splits, &ksps);
+    const size_t need = (size_t)splits * g.M * g.N * sizeof(float);
+    if (splits > 1 && ws_avail >= need) {
+      p.kind = PLAN_SPLITK; p.deep = 0; p.splits = splits; p.ksps = ksps; p.ws_bytes = need;
+      return p;
+    }
   }
-  if (need == 0 && (g.e.mode == VITMI_EPI_STORE || g.e.mode == VITMI_EPI_RESIDUAL) && g_tail_override != 0 &&
-      !g.e.colsum_part && !g.e.accumulate && (g.M % BM) == 0) {
+  // ---- split tail: no fused column sums, no accumulate, whole row tiles (the slices' workspace is M x N)
+  if ((e.mode == VITMI_EPI_STORE || e.mode == VITMI_EPI_RESIDUAL) && g_tail_override != 0 && !e.colsum_part && !e.accumulate && whole_m) {
     int rem, splits, ksps;
-    if (tail_plan_shape(g, tiles, &rem, &splits, &ksps, g_tail_override == 1)) need = tail_ws_bytes(g);
+    if (tail_plan_shape(g, nwg, &rem, &splits, &ksps, g_tail_override == 1) && rem <= NTHREADS && ws_avail >= tail_ws_bytes(g)) {
+      p.kind = g_tail_fixup ? PLAN_TAIL_FIXUP : PLAN_TAIL_FINISHER;
+      p.rem = rem; p.splits = splits; p.ksps = ksps; p.ws_bytes = tail_ws_bytes(g);
+    }
   }
-  return need;
+  return p;
 }
 
-static int gemm_fast_launch_whole(const GemmArgs& g, hipStream_t s) {
-  const EpiArgs& e = g.e;
-  const bool nt = g.a_km && g.b_km, nn = g.a_km && !g.b_km;
-#define GO(AKM, BKM, MODE) (e.c_bf16 ? launch<AKM, BKM, MODE, bf16>(g, s) : launch<AKM, BKM, MODE, float>(g, s))
-  switch (e.mode) {
-    case VITMI_EPI_STORE:
-      if (nt) return GO(true, true, VITMI_EPI_STORE);
-      if (nn) return GO(true, false, VITMI_EPI_STORE);
-      return GO(false, false, VITMI_EPI_STORE);
-    case VITMI_EPI_BIAS_GELU: return launch<true, true, VITMI_EPI_BIAS_GELU, bf16>(g, s);
-    case VITMI_EPI_RESIDUAL: return GO(true, true, VITMI_EPI_RESIDUAL);
-    case VITMI_EPI_DGELU: return launch<true, false, VITMI_EPI_DGELU, bf16>(g, s);
-    case VITMI_EPI_PATCH_POS: return GO(true, true, VITMI_EPI_PATCH_POS);
-  }
-#undef GO
-  return vitmi_fail(VITMI_E_SHAPE, "gemm_fast: combination not built");
+size_t gemm_fast_workspace(const GemmArgs& g) { return plan_fast(g, SIZE_MAX).ws_bytes; }
+
+int gemm_fast_launch(const GemmArgs& g, hipStream_t s) {
+  const FastPlan p = plan_fast(g, g.ws ? g.ws_bytes : 0);
+  if (p.kind == PLAN_TILE2_WHOLE || p.kind == PLAN_TILE2_SPLITK) return gemm_fast2_launch(g, p, s);
+  IssueFast f{g, p, s, 0};
+  if (!dispatch_combo(g, f)) return vitmi_fail(VITMI_E_SHAPE, "gemm_fast: combination not built");
+  return f.rc;
+}
+// the plan vitmi_gemm would follow (vitmi_debug_gemm_plan, gemm.hip)
+void gemm_fast_plan_query(const GemmArgs& g, int* kind, int* pipe, int* deep, int* splits) {
+  const FastPlan p = plan_fast(g, g.ws ? g.ws_bytes : 0);
+  *kind = p.kind; *pipe = p.pipe; *deep = p.deep; *splits = p.splits;
 }
 
 // ---- paired split-K launch (vitmi_gemm_pair): two weight-gradient products dW = dY^T X with the same K (all
@@ -1497,46 +1452,31 @@ static bool pair_ok(const GemmArgs& a, const GemmArgs& b) {
   };
   return plain(a) && plain(b) && a.K == b.K && a.launch_flags == b.launch_flags;
 }
-size_t gemm_fast_pair_workspace(const GemmArgs& a, const GemmArgs& b) {
-  if (!pair_ok(a, b)) return 0;
-  const int tiles = (int)(a.M / BM * (a.N / BN) + b.M / BM * (b.N / BN));
-  int splits, ksps;
-  splitk_plan(tiles, (int)(a.K / BK), &splits, &ksps);
-  if (splits <= 1) return 0;
-  return (size_t)splits * (a.M * a.N + b.M * b.N) * sizeof(float);
+struct PairPlan { int t1, t2, splits, ksps; size_t ws_bytes; };      // ws_bytes == 0: the pair cannot share a launch
+static PairPlan pair_plan(const GemmArgs& a, const GemmArgs& b) {
+  PairPlan p = {};
+  if (!pair_ok(a, b)) return p;
+  p.t1 = (int)(a.M / BM * (a.N / BN)); p.t2 = (int)(b.M / BM * (b.N / BN));
+  splitk_plan(p.t1 + p.t2, (int)(a.K / BK), SPLITK_MAX_TILES, g_splitk_target, &p.splits, &p.ksps);
+  if (p.splits > 1) p.ws_bytes = (size_t)p.splits * (a.M * a.N + b.M * b.N) * sizeof(float);
+  return p;
 }
+size_t gemm_fast_pair_workspace(const GemmArgs& a, const GemmArgs& b) { return pair_plan(a, b).ws_bytes; }
 // returns -1000 when the pair cannot share a launch (the caller then issues the two products one after the other)
 int gemm_fast_pair_launch(const GemmArgs& a_in, const GemmArgs& b, void* ws_, size_t ws_bytes, hipStream_t stream) {
-  const size_t need = gemm_fast_pair_workspace(a_in, b);
-  if (need == 0 || !ws_ || ws_bytes < need || !is_aligned(ws_, 16) || pipe_mode() == 0 || pipe_mode() == 2) return -1000;
+  const PairPlan p = pair_plan(a_in, b);
+  if (p.ws_bytes == 0 || !ws_ || ws_bytes < p.ws_bytes || !is_aligned(ws_, 16) || pipe_mode() == 0 || pipe_mode() == 2) return -1000;
   GemmArgs g = a_in;
-  const int t1 = (int)(g.M / BM * (g.N / BN)), t2 = (int)(b.M / BM * (b.N / BN));
-  int splits, ksps;
-  splitk_plan(t1 + t2, (int)(g.K / BK), &splits, &ksps);
   float* ws = reinterpret_cast<float*>(ws_);
   g.A2 = b.A; g.B2 = b.B; g.lda2 = b.lda; g.ldb2 = b.ldb; g.M2 = b.M; g.N2 = b.N;
-  g.tiles1 = t1; g.tiles_n2 = (int)(b.N / BN);
-  g.ws2 = ws + (size_t)splits * g.M * g.N;
+  g.tiles1 = p.t1; g.tiles_n2 = (int)(b.N / BN);
+  g.ws2 = ws + (size_t)p.splits * g.M * g.N;
   g.band = 0; g.stag_cycles = 0; g.stag_phases = 1; g.rfold = 0;
-  auto kern = gemm_fast_kernel<false, false, VITMI_EPI_STORE, float, true, 1>;
-  if (int rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(kern), 2 * STAGE_BYTES, "gemm_fast(pair)")) return rc;
-  const int nwg = (t1 + t2) * splits;
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(NTHREADS), 2 * STAGE_BYTES, stream, g, (int)(g.N / BN), nwg, t1 + t2, ksps, ws, 0);
-  if (int rc = vitmi_check_launch("gemm_fast_kernel(pair, split-K)")) return rc;
-  for (int i = 0; i < 2; ++i) {
-    const GemmArgs& p = i == 0 ? a_in : b;
-    const int64_t work = p.M * p.N / 4;
-    int64_t blocks = (work + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, i == 0 ? ws : g.ws2, splits, p.e, p.M, p.N);
-    if (int rc = vitmi_check_launch("splitk_reduce_kernel(pair)")) return rc;
-  }
-  return 0;
-}
-
-int gemm_fast_launch(const GemmArgs& g, hipStream_t s) {
-  if (use_tile2(g)) return gemm_fast2_launch(g, s);
-  return gemm_fast_launch_whole(g, s);
+  const int nwg = (p.t1 + p.t2) * p.splits;
+  if (int rc = launch_tiles(pick_kernel<false, false, VITMI_EPI_STORE, float>(1, true, false, 0), true, nwg, g, (int)(g.N / BN), nwg,
+                            p.t1 + p.t2, p.ksps, ws, 0, stream, "gemm_fast_kernel(pair, split-K)")) return rc;
+  if (int rc = launch_splitk_reduce(ws, p.splits, a_in.e, a_in.M, a_in.N, stream, "splitk_reduce_kernel(pair)")) return rc;
+  return launch_splitk_reduce(g.ws2, p.splits, b.e, b.M, b.N, stream, "splitk_reduce_kernel(pair)");
 }
 
 // every diagnostic switch of this file back to its default (vitmi_debug_reset, core.cpp)

@@ -363,37 +363,25 @@ inline int splitk_reduce2_waves(int64_t total4, int splits) {
 // whole step: target 512 / 384 / 256 / 192 / 128 -> CaiT-S24 19.74 / 19.59 / 19.37 / 19.59 /
 // 20.43 ms, Swin-T 16.33 / - / 16.05 / 16.29 / 17.04 ms).
 static std::atomic<int> g_splitk2_target{256};
-inline void splitk_plan2(int tiles, int nt, int* splits, int* ksps) {
-  int s = 1;
-  if (tiles <= 256 && nt >= 16) {
-    s = g_splitk2_target / tiles;
-    if (s > nt / 8) s = nt / 8;
-    if (s < 1) s = 1;
-  }
-  const int k = (nt + s - 1) / s;
-  *ksps = k;
-  *splits = (nt + k - 1) / k;
-}
 
+// issue what the plan says (gemm_fast2_plan below)
 template <bool A_KM, bool B_KM, int MODE, typename TC>
-int launch2(const GemmArgs& g, hipStream_t stream) {
+int launch2(const GemmArgs& g, const FastPlan& p, hipStream_t stream) {
   const int tiles_m = (int)((g.M + BM2 - 1) / BM2), tiles_n = (int)((g.N + BN2 - 1) / BN2);
   const int nwg = tiles_m * tiles_n;
   if constexpr (MODE == VITMI_EPI_STORE && sizeof(TC) == 4) {
-    int splits, ksps;
-    splitk_plan2(nwg, (int)(g.K / BK2), &splits, &ksps);
-    if (splits > 1 && g.ws && g.ws_bytes >= (size_t)splits * g.M * g.N * sizeof(float)) {
+    if (p.kind == PLAN_TILE2_SPLITK) {
       auto kern = gemm_fast2_kernel<A_KM, B_KM, MODE, TC, true>;
       if (int rc = vitmi_raise_dynamic_lds(reinterpret_cast<const void*>(kern), LDS2, "gemm_fast2(split-K)")) return rc;
       float* ws = reinterpret_cast<float*>(g.ws);
-      hipLaunchKernelGGL(kern, dim3(nwg * splits), dim3(NT2), LDS2, stream, g, tiles_n, nwg * splits, nwg, ksps, ws);
+      hipLaunchKernelGGL(kern, dim3(nwg * p.splits), dim3(NT2), LDS2, stream, g, tiles_n, nwg * p.splits, nwg, p.ksps, ws);
       int rc = vitmi_check_launch("gemm_fast2_kernel(split-K)");
       if (rc) return rc;
       const int64_t total4 = g.M * g.N / 4;
-      const int P = splitk_reduce2_waves(total4, splits);
+      const int P = splitk_reduce2_waves(total4, p.splits);
       int64_t blocks = (total4 + 63) / 64;
       if (blocks > 8192) blocks = 8192;
-      hipLaunchKernelGGL(splitk_reduce2_kernel, dim3((unsigned)blocks), dim3(64 * P), 0, stream, ws, splits, g.e, g.M, g.N);
+      hipLaunchKernelGGL(splitk_reduce2_kernel, dim3((unsigned)blocks), dim3(64 * P), 0, stream, ws, p.splits, g.e, g.M, g.N);
       return vitmi_check_launch("splitk_reduce2_kernel");
     }
   }
@@ -402,6 +390,10 @@ int launch2(const GemmArgs& g, hipStream_t stream) {
   hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT2), LDS2, stream, g, tiles_n, nwg, nwg, 0, (float*)nullptr);
   return vitmi_check_launch("gemm_fast2_kernel");
 }
+struct Issue2 {      // dispatch_combo functor
+  const GemmArgs& g; const FastPlan& p; hipStream_t s; int rc;
+  template <bool A_KM, bool B_KM, int MODE, typename TC> void operator()() { rc = launch2<A_KM, B_KM, MODE, TC>(g, p, s); }
+};
 
 }  // namespace
 
@@ -417,29 +409,24 @@ bool gemm_fast2_shape_ok(const GemmArgs& g) {
   return tiles < (1 << 30) && g.lda < (1 << 22) && g.ldb < (1 << 22);   // 32-bit per-lane offsets
 }
 
-size_t gemm_fast2_workspace(const GemmArgs& g) {
-  if (g.e.mode != VITMI_EPI_STORE || g.e.c_bf16) return 0;
+// the 256x128 part of plan_fast (gemm_fast.hip): split-K of the fp32 plain store where the workspace suffices
+FastPlan gemm_fast2_plan(const GemmArgs& g, size_t ws_avail) {
+  const int tiles = (int)(((g.M + BM2 - 1) / BM2) * ((g.N + BN2 - 1) / BN2)), nt = (int)(g.K / BK2);
+  FastPlan p = {};
+  p.kind = PLAN_TILE2_WHOLE;
+  p.splits = 1; p.ksps = nt;
+  if (g.e.mode != VITMI_EPI_STORE || g.e.c_bf16) return p;
   int splits, ksps;
-  splitk_plan2((int)(((g.M + BM2 - 1) / BM2) * ((g.N + BN2 - 1) / BN2)), (int)(g.K / BK2), &splits, &ksps);
-  return splits > 1 ? (size_t)splits * g.M * g.N * sizeof(float) : 0;
+  splitk_plan(tiles, nt, 256, g_splitk2_target, &splits, &ksps);
+  const size_t need = (size_t)splits * g.M * g.N * sizeof(float);
+  if (splits > 1 && ws_avail >= need) { p.kind = PLAN_TILE2_SPLITK; p.splits = splits; p.ksps = ksps; p.ws_bytes = need; }
+  return p;
 }
 
-int gemm_fast2_launch(const GemmArgs& g, hipStream_t s) {
-  const EpiArgs& e = g.e;
-  const bool nt = g.a_km && g.b_km, nn = g.a_km && !g.b_km;
-#define GO(AKM, BKM, MODE) (e.c_bf16 ? launch2<AKM, BKM, MODE, bf16>(g, s) : launch2<AKM, BKM, MODE, float>(g, s))
-  switch (e.mode) {
-    case VITMI_EPI_STORE:
-      if (nt) return GO(true, true, VITMI_EPI_STORE);
-      if (nn) return GO(true, false, VITMI_EPI_STORE);
-      return GO(false, false, VITMI_EPI_STORE);
-    case VITMI_EPI_BIAS_GELU: return launch2<true, true, VITMI_EPI_BIAS_GELU, bf16>(g, s);
-    case VITMI_EPI_RESIDUAL: return GO(true, true, VITMI_EPI_RESIDUAL);
-    case VITMI_EPI_DGELU: return launch2<true, false, VITMI_EPI_DGELU, bf16>(g, s);
-    case VITMI_EPI_PATCH_POS: return GO(true, true, VITMI_EPI_PATCH_POS);
-  }
-#undef GO
-  return vitmi_fail(VITMI_E_SHAPE, "gemm_fast2: combination not built");
+int gemm_fast2_launch(const GemmArgs& g, const FastPlan& p, hipStream_t s) {
+  Issue2 f{g, p, s, 0};
+  if (!dispatch_combo(g, f)) return vitmi_fail(VITMI_E_SHAPE, "gemm_fast2: combination not built");
+  return f.rc;
 }
 
 // every diagnostic switch of this file back to its default (vitmi_debug_reset, core.cpp)

@@ -362,3 +362,61 @@ __device__ __forceinline__ void epi_row(const EpiArgs& e, int64_t m, int64_t n, 
 
 constexpr int TRS = 68;                       // floats per row of the transpose strip (64 + pad)
 constexpr int TR_BYTES = 16 * TRS * 4;        // one wave's 16-row strip
+
+// ---- host side: what one tile-GEMM call launches, decided once (plan_fast, gemm_fast.hip) and followed by both the
+// workspace query and the launch
+enum FastPlanKind {
+  PLAN_WHOLE = 0,          // 256x256 tiles, one persistent launch
+  PLAN_SPLITK,             // 256x256, contraction split over workgroups + reduce
+  PLAN_TAIL_FINISHER,      // 256x256, full rounds + k-sliced remainder tiles + row-wise finisher
+  PLAN_TAIL_FIXUP,         // ... the last slice of a tile to arrive applies the epilogue itself
+  PLAN_TILE2_WHOLE,        // 256x128 tiles
+  PLAN_TILE2_SPLITK,
+};
+struct FastPlan {
+  int kind;                       // FastPlanKind
+  int pipe;                       // main-loop variant 0..3 (256x256 only)
+  int deep;                       // DEEP 0..2 of the main kernel's epilogue (256x256 only)
+  int splits, ksps;               // k-slices and k-steps per slice (1 / all when nothing is split)
+  int rem;                        // tail tiles (split tail only)
+  int band, stag_cycles, stag_phases, rfold;      // GemmArgs fields of the same names
+  size_t ws_bytes;                // workspace this plan needs
+};
+
+// Split-K rule of both tile sizes: a problem of `tiles` <= max_tiles output tiles and `nt` >= 16 k-steps is cut so
+// that about `target` workgroups run, each with at least 8 k-steps.
+inline void splitk_plan(int tiles, int nt, int max_tiles, int target, int* splits, int* ksps) {
+  int s = 1;
+  if (tiles <= max_tiles && nt >= 16) {
+    s = target / tiles;
+    if (s > nt / 8) s = nt / 8;
+    if (s < 1) s = 1;
+  }
+  const int k = (nt + s - 1) / s;
+  *ksps = k;
+  *splits = (nt + k - 1) / k;
+}
+
+// The (layout, epilogue, output dtype) combinations the tile kernels are built for: calls
+// f.operator()<A_KM, B_KM, MODE, TC>() for the one `g` asks for; false = not built.
+template <typename F>
+bool dispatch_combo(const GemmArgs& g, F&& f) {
+  const bool nt = g.a_km && g.b_km, nn = g.a_km && !g.b_km, tn = !g.a_km && !g.b_km;
+  const bool c16 = g.e.c_bf16 != 0;
+#define VITMI_COMBO(AKM, BKM, MODE, TC) (f.template operator()<AKM, BKM, MODE, TC>(), true)
+  switch (g.e.mode) {
+    case VITMI_EPI_STORE:
+      if (nt) return c16 ? VITMI_COMBO(true, true, VITMI_EPI_STORE, bf16) : VITMI_COMBO(true, true, VITMI_EPI_STORE, float);
+      if (nn) return c16 ? VITMI_COMBO(true, false, VITMI_EPI_STORE, bf16) : VITMI_COMBO(true, false, VITMI_EPI_STORE, float);
+      if (tn) return c16 ? VITMI_COMBO(false, false, VITMI_EPI_STORE, bf16) : VITMI_COMBO(false, false, VITMI_EPI_STORE, float);
+      return false;
+    case VITMI_EPI_BIAS_GELU: return nt && c16 && VITMI_COMBO(true, true, VITMI_EPI_BIAS_GELU, bf16);
+    case VITMI_EPI_RESIDUAL:
+      return nt && (c16 ? VITMI_COMBO(true, true, VITMI_EPI_RESIDUAL, bf16) : VITMI_COMBO(true, true, VITMI_EPI_RESIDUAL, float));
+    case VITMI_EPI_DGELU: return nn && c16 && VITMI_COMBO(true, false, VITMI_EPI_DGELU, bf16);
+    case VITMI_EPI_PATCH_POS:
+      return nt && (c16 ? VITMI_COMBO(true, true, VITMI_EPI_PATCH_POS, bf16) : VITMI_COMBO(true, true, VITMI_EPI_PATCH_POS, float));
+  }
+#undef VITMI_COMBO
+  return false;
+}
