@@ -251,6 +251,7 @@ inline int colsum_splits(int64_t M) {
 
 // ------------------------------------------------------------------ xent --
 // one wave per sample; K classes strided over lanes
+constexpr float XENT_LSE_SWITCH = 16.f;
 __global__ __launch_bounds__(256) void xent_kernel(const float* __restrict__ logits,
                                                    const int64_t* __restrict__ labels,
                                                    float* __restrict__ loss_rows,
@@ -277,12 +278,18 @@ __global__ __launch_bounds__(256) void xent_kernel(const float* __restrict__ log
   float se = 0.f;
   for (int k = lane; k < K; k += 64) se += __expf(lr[k] - mx);
   se = wave_sum(se);
-  const float lse = mx + __logf(se);
+  // log p[k] = x[k] - lse with lse = mx + log(se).  While |lse| < XENT_LSE_SWITCH the sum keeps log(se) to 2^-21 and
+  // the loss and every p are formed from lse, bit for bit as they always were.  Beyond it lse rounds log(se) to the
+  // spacing of mx (2^-9 at |mx| = 3e4: 8e-4 in the loss and in every p), so the row is worked relative to its maximum,
+  // log p[k] = (x[k] - mx) - log(se), where every difference is small.  (NaN logits take that form too.)
+  const float lg = __logf(se);
+  const float lse = mx + lg;
+  const bool rel = !(fabsf(lse) < XENT_LSE_SWITCH);      // wave-uniform
   const int64_t lab = labels[b];
   const float invB = 1.f / (float)B;
   if (dlogits) {
     for (int k = lane; k < K; k += 64) {
-      const float p = __expf(lr[k] - lse);
+      const float p = rel ? __expf((lr[k] - mx) - lg) : __expf(lr[k] - lse);
       dlogits[b * K + k] = (p - (k == lab ? 1.f : 0.f)) * invB;
     }
   }
@@ -290,7 +297,8 @@ __global__ __launch_bounds__(256) void xent_kernel(const float* __restrict__ log
     // a label outside [0, K) must not become an out-of-bounds read: its sample's loss (and
     // with it the mean) is NaN, which the host sees at the next .item()
     const bool ok = lab >= 0 && lab < (int64_t)K;
-    loss_rows[b] = ok ? lse - lr[ok ? lab : 0] : __builtin_nanf("");
+    const float xl = lr[ok ? lab : 0];
+    loss_rows[b] = ok ? (rel ? lg - (xl - mx) : lse - xl) : __builtin_nanf("");
     correct_rows[b] = (ok && amax == (int)lab) ? 1 : 0;
   }
 }
