@@ -534,6 +534,13 @@ __global__ __launch_bounds__(NTHREADS) void gemm_fast_kernel(GemmArgs g, int til
     }
   };
 
+  // epilogue addressing of the gelu'-multiply (uniform_ptr / lane_ptr, gemm_tile.h): the lane's byte offset inside a row
+  // group of C and of AUX — tile independent
+  // (no other epilogue has them: zero there)
+  constexpr bool SADDR = MODE == VITMI_EPI_DGELU && !SPLITK;
+  const uint32_t vo_c = SADDR ? lane_off(lane / LPR, (lane % LPR) * W, g.e.ldc, (int)sizeof(TC)) : 0u;
+  const uint32_t vo_s = SADDR ? lane_off(lane / LPR, (lane % LPR) * W, g.e.ldaux, 2) : 0u;
+
   if (PERSIST && idx >= x_len) return;
   const int tiles_m = (int)((pM + BM - 1) / BM);
   int mt_, nt_;
@@ -856,6 +863,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_fast_kernel(GemmArgs g, int til
   float cs[W];                                     // DGELU: column sums of this lane's rows
 #pragma unroll
   for (int i = 0; i < W; ++i) cs[i] = 0.f;
+  // ragged M: only the last row tile has padding rows to keep out of the column sums (workgroup-uniform)
+  const bool full_m = m0 + BM <= pM;
+  // the wave's quadrant of the tile, in elements of an array with leading dimension ld (wave-uniform)
+  auto quad_off = [&](int64_t mrow0, int64_t ld) { return (mrow0 + wm * 128) * ld + n0 + wn * 64; };
   // DEEP (bf16 outputs with a per-element side input: the bf16 residual stream, the saved gelu'): THREE strips of the side
   // input in flight, kept packed (4 registers per 16-B piece: 24 registers, fewer than the two unpacked strips of round 2).
   // One strip ahead gives a load the ~1.9 k cycles a strip takes to process; under the epilogue burst of all CUs an HBM
@@ -869,11 +880,25 @@ __global__ __launch_bounds__(NTHREADS) void gemm_fast_kernel(GemmArgs g, int til
       const bf16* sbase = MODE == VITMI_EPI_RESIDUAL ? reinterpret_cast<const bf16*>(g.e.R) : reinterpret_cast<const bf16*>(g.e.AUX);
       const int64_t sld = MODE == VITMI_EPI_RESIDUAL ? g.e.ldr : g.e.ldaux;
       bf16x8 sp[3][NJ];
-      auto side_load = [&](int strip, bf16x8 (&dst)[NJ]) {
+      // SADDR (the gelu'-multiply only): scalar row bases of AUX and of C,
+      // each walking its row groups in order, RPI rows at a time; the residual path keeps row_off
+      const int64_t s_step = RPI * sld * 2, c_step = RPI * g.e.ldc * (int64_t)sizeof(TC);
+      gbase_t s_row = nullptr, c_row = nullptr;
+      if constexpr (SADDR) {
+        s_row = uniform_ptr(sbase, quad_off(m0, sld) * 2);
+        c_row = uniform_ptr(g.e.C, quad_off(m0, g.e.ldc) * (int64_t)sizeof(TC));
+      }
+      auto side_load = [&](int strip, bf16x8 (&dst)[NJ]) {      // (strips are loaded in order)
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-          const bf16x8* p = reinterpret_cast<const bf16x8*>(sbase + row_off(m0 + wm * 128 + strip * 16 + j * RPI, rr, sld, ncol));
-          dst[j] = g.e.side_nt ? __builtin_nontemporal_load(p) : *p;
+          if constexpr (SADDR) {
+            const auto p = lane_ptr<const bf16x8>(s_row, vo_s);
+            dst[j] = g.e.side_nt ? __builtin_nontemporal_load(p) : *p;
+            s_row += s_step;
+          } else {
+            const bf16x8* p = reinterpret_cast<const bf16x8*>(sbase + row_off(m0 + wm * 128 + strip * 16 + j * RPI, rr, sld, ncol));
+            dst[j] = g.e.side_nt ? __builtin_nontemporal_load(p) : *p;
+          }
         }
       };
       side_load(0, sp[0]);
@@ -887,6 +912,9 @@ __global__ __launch_bounds__(NTHREADS) void gemm_fast_kernel(GemmArgs g, int til
       // branches on those run-time options around loads and stores; at every join hipcc must assume the conditional
       // store / load may not have been issued and its counted waits turn into drains (ISA: vmcnt(0) in front of every row
       // of the residual strip; vmcnt(5) where nine operations could have stayed in flight in the gelu' one).
+      // Column sums of the gelu' path: only the last row tile of a ragged M selects per row; every other tile adds
+      // unconditionally (same order of additions within a lane).  As a branch inside the row loop: two copies of the
+      // whole loop made hipcc spill.
       auto deep_loop = [&](auto plain_tag) {
         constexpr bool PLAIN = decltype(plain_tag)::value;
 #pragma unroll
@@ -915,14 +943,20 @@ __global__ __launch_bounds__(NTHREADS) void gemm_fast_kernel(GemmArgs g, int til
               bf16x8 o;
 #pragma unroll
               for (int i = 0; i < W; ++i) o[i] = (bf16)v[i];
-              __builtin_nontemporal_store(o, reinterpret_cast<bf16x8*>(reinterpret_cast<TC*>(g.e.C) + row_off(m0 + wm * 128 + mi * 16 + j * RPI, rr, g.e.ldc, ncol)));
+              __builtin_nontemporal_store(o, lane_ptr<bf16x8>(c_row, vo_c));
             } else {
               epi_row<MODE, TC, W>(g.e, m0 + wm * 128 + mi * 16 + j * RPI, rr, ncol, v, bias_r, gamma_r, x);
             }
+            if constexpr (SADDR) c_row += c_step;
             if constexpr (MODE == VITMI_EPI_DGELU) {
-              const bool in_m = m0 + wm * 128 + mi * 16 + j * RPI + rr < pM;      // ragged M: the padding rows stay out of the column sums
+              if (full_m) {                            // workgroup-uniform; no memory operation on either side
 #pragma unroll
-              for (int i = 0; i < W; ++i) cs[i] += in_m ? v[i] : 0.f;
+                for (int i = 0; i < W; ++i) cs[i] += v[i];
+              } else {
+                const bool in_m = m0 + wm * 128 + mi * 16 + j * RPI + rr < pM;      // the padding rows stay out of the column sums
+#pragma unroll
+                for (int i = 0; i < W; ++i) cs[i] += in_m ? v[i] : 0.f;
+              }
             }
           }
           if (mi + 3 < 8) side_load(mi + 3, sp[mi % 3]);
@@ -985,9 +1019,14 @@ __global__ __launch_bounds__(NTHREADS) void gemm_fast_kernel(GemmArgs g, int til
       } else {
         epi_row<MODE, TC, W>(g.e, m0 + wm * 128 + mi * 16 + j * RPI, rr, ncol, v, bias_r, gamma_r, sx[mi & 1][j]);
         if constexpr (MODE == VITMI_EPI_DGELU) {
-          const bool in_m = m0 + wm * 128 + mi * 16 + j * RPI + rr < pM;
+          if (full_m) {                                // workgroup-uniform; no memory operation on either side
 #pragma unroll
-          for (int i = 0; i < W; ++i) cs[i] += in_m ? v[i] : 0.f;
+            for (int i = 0; i < W; ++i) cs[i] += v[i];
+          } else {
+            const bool in_m = m0 + wm * 128 + mi * 16 + j * RPI + rr < pM;
+#pragma unroll
+            for (int i = 0; i < W; ++i) cs[i] += in_m ? v[i] : 0.f;
+          }
         }
       }
     }
@@ -1361,6 +1400,13 @@ bool gemm_fast_supported(const GemmArgs& g, int in_bf16) {
   if (e.mode == VITMI_EPI_DGELU && (e.ldaux % 4 || !is_aligned(e.AUX, 8))) return false;
   if (e.mode == VITMI_EPI_PATCH_POS && (!is_aligned(e.pos, 16) || (e.cls && !is_aligned(e.cls, 16)))) return false;
   if (e.mode == VITMI_EPI_STORE && e.accumulate && e.c_bf16) return false;
+  // an epilogue may address a row group as scalar base + 32-bit lane offset (lane_off, gemm_tile.h; today the
+  // gelu'-multiply does, for C and AUX): no array may reach 2^31 with that offset, whatever the epilogue
+  const int c_rpi = e.c_bf16 ? 8 : 4, c_esz = e.c_bf16 ? 2 : 4;
+  if (!lane_off_fits(e.ldc, c_rpi, c_esz)) return false;
+  if (e.C2 && !lane_off_fits(e.ldc2, c_rpi, c_esz)) return false;      // (C's figures: conservative where C2 is bf16 beside an fp32 C)
+  if (e.mode == VITMI_EPI_RESIDUAL && !lane_off_fits(e.ldr, c_rpi, c_esz)) return false;
+  if (e.mode == VITMI_EPI_DGELU && !lane_off_fits(e.ldaux, 8, 2)) return false;
   return true;
 }
 

@@ -265,6 +265,35 @@ __device__ __forceinline__ bool epi_has_side(const EpiArgs& e) {
 __device__ __forceinline__ int64_t row_off(int64_t mu, int64_t ml, int64_t ld, int64_t n) {
   return mu * ld + (ml * ld + n);
 }
+// The gelu'-multiply epilogue of the 256x256 kernel goes one step further and keeps vector arithmetic out of the addresses
+// altogether.  Per tile and array, the wave-uniform part (pointer, tile origin, the wave's quadrant) is ONE 64-bit byte
+// address in scalar registers, stepped from row group to row group with scalar adds; the lane's part
+// (ml * ld + column) * esz is a 32-bit byte offset, the same for every row group and every tile of a launch.  The base
+// is rebuilt from readfirstlane'd halves, which would leave the compiler without the pointer's address space (it then
+// emits FLAT operations, which count in lgkmcnt too): both helpers therefore carry an explicit global (address space 1)
+// pointer type, and an access through lane_ptr is a global_load / global_store with a scalar base and a vector offset.
+// The offset is below (RPI * ld + 64) * esz; gemm_fast_supported refuses leading dimensions at which that would not fit
+// 31 bits.
+#define VITMI_GLOBAL_AS __attribute__((address_space(1)))
+typedef VITMI_GLOBAL_AS const char* gbase_t;
+__device__ __forceinline__ gbase_t uniform_ptr(const void* p, int64_t byte_off) {
+  const uint64_t a = (uint64_t)(uintptr_t)p + (uint64_t)byte_off;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+  return (gbase_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ uint32_t lane_off(int ml, int col, int64_t ld, int esz) {
+  return ((uint32_t)ml * (uint32_t)ld + (uint32_t)col) * (uint32_t)esz;
+}
+template <typename V>
+__device__ __forceinline__ VITMI_GLOBAL_AS V* lane_ptr(gbase_t base, uint32_t voff) {
+  // (the empty asm keeps the zero-extension next to the access: hoisted out of the tile loop as a 64-bit pair, the
+  // offset no longer shows the instruction selector that its upper half is zero, and the scalar-base form is not chosen)
+  asm volatile("" : "+v"(voff));
+  return (VITMI_GLOBAL_AS V*)(base + (uint64_t)voff);
+}
+// the host-side bound that goes with lane_off: rows per wave instruction `rpi`, element size `esz`
+inline bool lane_off_fits(int64_t ld, int rpi, int esz) { return ((int64_t)rpi * ld + 64) * esz < (1ll << 31); }
+
 template <int MODE, typename TC, int W>
 __device__ __forceinline__ void epi_side(const EpiArgs& e, int64_t mu, int64_t ml, int64_t n, float (&x)[W]) {
   if constexpr (MODE == VITMI_EPI_RESIDUAL) {
