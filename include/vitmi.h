@@ -371,6 +371,18 @@ int vitmi_ca_out_fwd(const float* xc, int64_t xc_stride, const float* xp, const 
 int vitmi_ca_out_bwd(const float* G, const float* gamma2, float* dx2, void* gm, int dtype, int64_t B, int64_t N1,
                      int64_t D, void* stream);
 
+/* The middle junction of XCiT's XCABlock (models/xcit.py:290-291), whose second branch ends in the LPI kernel and not in a
+ * product: y = x + gamma * b (the LayerScale residual) and l = LayerNorm(y) (the next branch's norm) in one pass, the row
+ * held in registers between the two.  Additive to ABI 109.
+ *   x, y: fp32 [M, D], the residual stream; y may be x (in place).  b, l: `dtype` (bf16 or fp32) [M, D], the branch output
+ *   and the normed rows.  gamma, ln_weight, ln_bias fp32 [D].  mean, rstd fp32 [M] (of y; two-pass, fp32).
+ *   Everything contiguous, every pointer 16-byte aligned; D a multiple of 8 with 8 <= D <= 2048; M >= 1 (M < 2^31).
+ * Anything else fails before any launch.  No workspace, no atomics. */
+int vitmi_ls_residual_ln_supported(int dtype, int64_t M, int64_t D);
+int vitmi_ls_residual_ln_fwd(const float* x, const void* b, const float* gamma, const float* ln_weight,
+                             const float* ln_bias, float* y, void* l, float* mean, float* rstd, int dtype, int64_t M,
+                             int64_t D, float eps, void* stream);
+
 /* ------------------------------------------------------------- CaiT ops --
  * Talking-heads softmax (models/cait.py:118-122) on score tensors [B,H,N,ld] (row length
  * Nk <= 1024 valid columns, H <= 16; other shapes fail with VITMI_E_SHAPE before any launch):

@@ -8,8 +8,8 @@ from .cait import cait_models  # noqa: F401
 from .swin import SwinTransformer  # noqa: F401
 from .graph import GraphedStep  # noqa: F401
 from .head import ClassifierHead  # noqa: F401
-from .xcit import XCA, LPI, ConvPatchEmbed, PositionalEncodingFourier, ClassAttentionBlock  # noqa: F401
+from .xcit import XCA, LPI, ConvPatchEmbed, PositionalEncodingFourier, ClassAttentionBlock, XCABlock  # noqa: F401
 from .checkpoint import load_reference_checkpoint  # noqa: F401
 from .stats import RunLog  # noqa: F401
 
-__all__ = ["VisionModelZoo", "VisionTransformer", "CrossEntropyLoss", "FusedSGD", "FusedAdamW", "FusedAdagrad", "FusedAdadelta", "FusedAdaBelief", "GraphedStep", "ClassifierHead", "XCA", "LPI", "ConvPatchEmbed", "PositionalEncodingFourier", "ClassAttentionBlock", "load_reference_checkpoint", "RunLog", "VitmiError"]
+__all__ = ["VisionModelZoo", "VisionTransformer", "CrossEntropyLoss", "FusedSGD", "FusedAdamW", "FusedAdagrad", "FusedAdadelta", "FusedAdaBelief", "GraphedStep", "ClassifierHead", "XCA", "LPI", "ConvPatchEmbed", "PositionalEncodingFourier", "ClassAttentionBlock", "XCABlock", "load_reference_checkpoint", "RunLog", "VitmiError"]

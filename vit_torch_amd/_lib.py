@@ -114,6 +114,8 @@ SIGNATURES = {
     "vitmi_ca_merge_bwd": (C.c_int, [c_vp] * 7 + [C.c_int, c_i64, c_i64, c_i64, c_vp, c_sz, c_vp]),
     "vitmi_ca_out_fwd": (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, C.c_int, c_i64, c_i64, c_i64, c_vp]),
     "vitmi_ca_out_bwd": (C.c_int, [c_vp] * 4 + [C.c_int, c_i64, c_i64, c_i64, c_vp]),
+    "vitmi_ls_residual_ln_supported": (C.c_int, [C.c_int, c_i64, c_i64]),
+    "vitmi_ls_residual_ln_fwd": (C.c_int, [c_vp] * 9 + [C.c_int, c_i64, c_i64, C.c_float, c_vp]),
     "vitmi_attn_bwd_workspace": (c_sz, [c_i64, c_i64, c_i64]),
     "vitmi_attn_bwd_dbias_rows": (c_i64, [c_i64, c_i64]),
     "vitmi_attn_bwd": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int, c_i64, c_i64, c_i64, c_i64,

@@ -702,6 +702,35 @@ def ca_out_bwd(G, gamma2, dx2, gm, B, N1, D):
     return dx2
 
 
+def ls_residual_ln_supported(t, M, D) -> bool:
+    """Host-only query: does ls_residual_ln_fwd take this branch dtype and shape (D a multiple of 8, 8 <= D <= 2048)?"""
+    return bool(load().vitmi_ls_residual_ln_supported(dtype_code_or_neg(t), M, D))
+
+
+def ls_residual_ln_fwd(x, b, gamma, ln_weight, ln_bias, y, l, mean, rstd, eps, *, M=None, D=None):
+    """y = x + gamma * b and l = LayerNorm(y) in one pass (vitmi_ls_residual_ln_fwd): the junction of a LayerScale residual
+    branch that does not end in a GEMM and the norm that reads the sum.  x, y fp32 [M, D] (y may be x); b, l [M, D] in one
+    dtype, bf16 or fp32; gamma, ln_weight, ln_bias fp32 [D]; mean, rstd fp32 [M], of y."""
+    _need_cuda(x, b, gamma, ln_weight, ln_bias, y, l, mean, rstd)
+    D = D or x.shape[-1]
+    M = M or x.numel() // D
+    if not ls_residual_ln_supported(b, M, D):
+        raise _lib.VitmiError(f"ls_residual_ln_fwd: unsupported (needs bf16 or fp32 b / l, M >= 1 and D a multiple of 8 with "
+                              f"8 <= D <= 2048; got {b.dtype}, M {M}, D {D})")
+    for name, t in (("x", x), ("y", y)):
+        _contract("ls_residual_ln_fwd", name, t, torch.float32, M * D, f"[M, D] = [{M}, {D}]")
+    for name, t in (("b", b), ("l", l)):
+        _contract("ls_residual_ln_fwd", name, t, b.dtype, M * D, f"[M, D] = [{M}, {D}]")
+    for name, t in (("gamma", gamma), ("ln_weight", ln_weight), ("ln_bias", ln_bias)):
+        _contract("ls_residual_ln_fwd", name, t, torch.float32, D, f"[D] = [{D}]")
+    for name, t in (("mean", mean), ("rstd", rstd)):
+        _contract("ls_residual_ln_fwd", name, t, torch.float32, M, f"[M] = [{M}]")
+    check(load().vitmi_ls_residual_ln_fwd(x.data_ptr(), b.data_ptr(), gamma.data_ptr(), ln_weight.data_ptr(), ln_bias.data_ptr(),
+                                          y.data_ptr(), l.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dtype_code(b), M, D,
+                                          float(eps), _stream()), "vitmi_ls_residual_ln_fwd")
+    return y
+
+
 def attn_bwd_dbias_rows(B, N) -> int:
     return int(load().vitmi_attn_bwd_dbias_rows(B, N))
 

@@ -1,5 +1,6 @@
 """XCiT's cross-covariance attention (XCA), local patch interaction (LPI), convolutional patch embedding (ConvPatchEmbed),
-Fourier positional encoding (PositionalEncodingFourier) and class-attention block (ClassAttentionBlock) on libvitmi kernels.
+Fourier positional encoding (PositionalEncodingFourier), class-attention block (ClassAttentionBlock) and trunk block (XCABlock)
+on libvitmi kernels.
 
 `XCA` is the attention module of the reference's `models/xcit.py:221-261`: a qkv Linear, attention over CHANNELS
 (q and k L2-normalised along the token axis, a learnable per-head temperature, a softmax over an hd x hd map per head)
@@ -32,7 +33,16 @@ which doubles the patch rows.  The element-wise steps between the GEMMs are the 
 State-dict keys are the reference's (`norm1.*`, `attn.qkv.*`, `attn.proj.*`, `norm2.*`, `mlp.fc1.*`, `mlp.fc2.*`, `gamma1`,
 `gamma2`).
 
-Of XCiT, only the engine that composes these modules (and its zoo entry) is not built.
+`XCABlock` is the reference's `models/xcit.py:264-292`, the block of XCiT's trunk: `x + gamma1 * attn(norm1(x))`, `x + gamma3 *
+local_mp(norm3(x), H, W)`, `x + gamma2 * mlp(norm2(x))`.  One module with one pack on the XCA and LPI kernels (it does not nest
+the `XCA` and `LPI` modules), LayerNorm and the GEMMs: the attention and MLP branches end in a Linear, so the product's
+`EPI_RESIDUAL` epilogue does their LayerScale residual; the LPI branch ends in no product, and its residual and the norm2 that
+reads the sum are one kernel (`ops.ls_residual_ln_fwd`, `xcit_glue.hip`).  The backward uses existing ops only.  State-dict
+keys, shapes and order are the reference's (`gamma1`, `gamma2`, `gamma3`, `norm1.*`, `attn.temperature`, `attn.qkv.*`,
+`attn.proj.*`, `norm2.*`, `mlp.fc1.*`, `mlp.fc2.*`, `norm3.*`, `local_mp.conv1.*`, `local_mp.bn.*` with the three running
+buffers, `local_mp.conv2.*`).
+
+Of XCiT, the model that stacks these modules, its engine and its zoo entries are not built.
 
 Stand-alone modules on `engine.PackedModule`, as `ClassifierHead` is: the parameters live in a `ParamPack` (the fused
 optimizers update them), forward and backward run through the mixin's one `torch.autograd.Function`; each class here
@@ -42,7 +52,7 @@ shadows; "fp32": everything in fp32.  LPI: bf16 or fp32 activations, every param
 ConvPatchEmbed: bf16 or fp32 activations, the GEMMs on the bf16 weight shadows in "bf16", the norm parameters and every
 gradient in fp32.  PositionalEncodingFourier: the feature table and the GEMM operands in the compute dtype, the encoding,
 the sum and every gradient in fp32.  ClassAttentionBlock: the residual stream in fp32, the branch tensors and GEMM operands
-in the compute dtype.  CPU tensors raise: there is no fallback.
+in the compute dtype.  XCABlock: the same.  CPU tensors raise: there is no fallback.
 """
 from __future__ import annotations
 
@@ -50,7 +60,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import EPI_BIAS_GELU, EPI_DGELU, VitmiError
+from ._lib import EPI_BIAS_GELU, EPI_DGELU, EPI_RESIDUAL, VitmiError
 from .engine import PackedModule
 
 
@@ -403,10 +413,10 @@ class PositionalEncodingFourier(PackedModule, nn.Module):
 
 
 class _ParamHolder(nn.Module):
-    """holds Linear layers under the reference's names; never called"""
+    """holds parameters, buffers and layers under the reference's names; never called"""
 
     def forward(self, *a, **k):
-        raise VitmiError("this submodule only holds parameters; call the ClassAttentionBlock")
+        raise VitmiError("this submodule only holds parameters; call the block that owns it")
 
 
 class ClassAttentionBlock(PackedModule, nn.Module):
@@ -564,3 +574,156 @@ class ClassAttentionBlock(PackedModule, nn.Module):
         ops.layernorm_bwd(dlm, xa, mean1, rstd1, pk.f32(self.norm1.weight), dx1, dx1, None, pk.g(self.norm1.weight),
                           pk.g(self.norm1.bias), M=M, D=D)
         return dx1 if need_dx else None
+
+
+class XCABlock(PackedModule, nn.Module):
+    """XCiT's trunk block: `forward(x, H, W)` with x [B, H*W, dim] returns the fp32 [B, H*W, dim] tensor of the reference's
+    block, three LayerScale residual branches: cross-covariance attention, local patch interaction on the H x W grid, MLP.
+    `num_tokens` and `qk_scale` are accepted and unused, as there.  `attn` (`temperature`, `qkv`, `proj`), `mlp` (`fc1`,
+    `fc2`) and `local_mp` (`conv1`, `bn`, `conv2`) only hold the parameters and buffers under the reference's names.
+    `.train()` / `.eval()` select batch or running statistics for the LPI's batch norm; in training the forward updates
+    the running buffers on the device, as `LPI` does (per process: no cross-rank exchange).
+
+    Kept for the backward: x, x1, x2 (fp32), the three norms' statistics, and in the compute dtype l1 = norm1(x), qkv, the
+    attention output and its stat, f1 = proj(...), l3 = norm3(x1), the LPI's u and stat, p = lpi(l3), l2 = norm2(x2), the
+    MLP's pre-activation (its gelu' in "bf16"), the hidden rows and f2 = fc2(...)."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, qk_scale=None, drop=0., attn_drop=0., drop_path=0.,
+                 act_layer=nn.GELU, norm_layer=nn.LayerNorm, num_tokens=196, eta=None, compute_dtype="bf16"):
+        super().__init__()
+        if compute_dtype not in ("bf16", "fp32"):
+            raise VitmiError(f"XCABlock: compute_dtype must be 'bf16' or 'fp32', got {compute_dtype!r}")
+        for name, v in (("drop", drop), ("attn_drop", attn_drop), ("drop_path", drop_path)):
+            if v != 0.:
+                raise VitmiError(f"XCABlock: {name} = {v} is not built (dropout and drop_path: the kernels have no mask)")
+        if act_layer is not nn.GELU:
+            raise VitmiError("XCABlock: only nn.GELU (erf form) is built as the activation")
+        if eta is None:
+            raise VitmiError("XCABlock: eta=None is not built: the reference's own constructor fails on it (eta * ones)")
+        if dim % num_heads or dim // num_heads not in (32, 48, 64):
+            raise VitmiError(f"XCABlock: head dim {dim}/{num_heads} not in {{32, 48, 64}} (the XCA kernels' limit)")
+        hidden = int(dim * mlp_ratio)
+        if dim % 8 or hidden < 8 or hidden % 8:
+            raise VitmiError(f"XCABlock: dim {dim} and the MLP's hidden width {hidden} must be multiples of 8")
+        self.dim, self.num_heads, self.compute_dtype = dim, num_heads, compute_dtype
+        self.norm1 = norm_layer(dim)
+        self.attn = _ParamHolder()
+        self.attn.temperature = nn.Parameter(torch.ones(num_heads, 1, 1))
+        self.attn.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
+        self.attn.proj = nn.Linear(dim, dim)
+        self.norm2 = norm_layer(dim)
+        self.mlp = _ParamHolder()
+        self.mlp.fc1 = nn.Linear(dim, hidden)
+        self.mlp.fc2 = nn.Linear(hidden, dim)
+        self.norm3 = norm_layer(dim)
+        self.local_mp = _ParamHolder()
+        self.local_mp.conv1 = nn.Conv2d(dim, dim, kernel_size=3, padding=1, groups=dim)
+        self.local_mp.bn = nn.BatchNorm2d(dim)
+        self.local_mp.conv2 = nn.Conv2d(dim, dim, kernel_size=3, padding=1, groups=dim)
+        for n in (self.norm1, self.norm2, self.norm3):
+            if not isinstance(n, nn.LayerNorm) or not n.elementwise_affine or tuple(n.normalized_shape) != (dim,):
+                raise VitmiError("XCABlock: norm_layer must build an affine nn.LayerNorm over dim")
+        self.gamma1 = nn.Parameter(eta * torch.ones(dim))
+        self.gamma2 = nn.Parameter(eta * torch.ones(dim))
+        self.gamma3 = nn.Parameter(eta * torch.ones(dim))
+        self.pack_shadow = compute_dtype == "bf16"        # the GEMMs read the bf16 weight shadows
+
+    def forward(self, x, H, W):
+        self._refuse_cpu(x)
+        if x.dim() != 3 or x.shape[-1] != self.dim:
+            raise VitmiError(f"XCABlock: input must be [B, H*W, {self.dim}], got {tuple(x.shape)}")
+        if H < 1 or W < 1 or x.shape[1] != H * W:
+            raise VitmiError(f"XCABlock: {x.shape[1]} tokens are not an H x W = {H} x {W} grid")
+        return self._run(x, H, W)
+
+    # ---- kernels
+    def _forward(self, x, Hg, Wg, save):
+        B, N, D = x.shape
+        H, hd, pk, M = self.num_heads, D // self.num_heads, self._pack, B * N
+        a_, mlp, lp, dev, f32 = self.attn, self.mlp, self.local_mp, x.device, torch.float32
+        T = torch.bfloat16 if self.compute_dtype == "bf16" else f32
+        new = lambda *shape, dtype=T: torch.empty(shape, dtype=dtype, device=dev)      # noqa: E731
+        pk.refresh_shadow()
+        xa = x.float().contiguous().view(M, D)
+        # x1 = x + gamma1 * attn(norm1(x))
+        l1, mean1, rstd1 = new(M, D), new(M, dtype=f32), new(M, dtype=f32)
+        ops.layernorm_fwd(xa, pk.f32(self.norm1.weight), pk.f32(self.norm1.bias), l1, mean1, rstd1, self.norm1.eps, M=M, D=D)
+        qkv = new(M, 3 * D)
+        ops.gemm(l1, pk.w(a_.qkv.weight), qkv, bias=pk.f32(a_.qkv.bias) if a_.qkv.bias is not None else None)
+        att, stat = new(M, D), new(B, H, hd + 2, hd, dtype=f32)
+        ops.xca_fwd(qkv, pk.f32(a_.temperature).view(H), att, stat, B, N, H, hd)
+        x1, f1 = new(M, D, dtype=f32), new(M, D)
+        ops.gemm(att, pk.w(a_.proj.weight), x1, epilogue=EPI_RESIDUAL, bias=pk.f32(a_.proj.bias), R=xa, gamma=pk.f32(self.gamma1),
+                 C2=f1)
+        # x2 = x1 + gamma3 * local_mp(norm3(x1)), and l2 = norm2(x2) in the same pass
+        l3, mean3, rstd3 = new(M, D), new(M, dtype=f32), new(M, dtype=f32)
+        ops.layernorm_fwd(x1, pk.f32(self.norm3.weight), pk.f32(self.norm3.bias), l3, mean3, rstd3, self.norm3.eps, M=M, D=D)
+        u, p, lstat, bn = new(M, D), new(M, D), new(2, D, dtype=f32), lp.bn
+        ops.lpi_fwd(l3, pk.f32(lp.conv1.weight), pk.f32(lp.conv1.bias), pk.f32(bn.weight), pk.f32(bn.bias),
+                    pk.f32(lp.conv2.weight), pk.f32(lp.conv2.bias), bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                    u, lstat, p, B, Hg, Wg, D, training=self.training, momentum=bn.momentum, eps=bn.eps)
+        x2, l2, mean2, rstd2 = new(M, D, dtype=f32), new(M, D), new(M, dtype=f32), new(M, dtype=f32)
+        ops.ls_residual_ln_fwd(x1, p, pk.f32(self.gamma3), pk.f32(self.norm2.weight), pk.f32(self.norm2.bias), x2, l2, mean2,
+                               rstd2, self.norm2.eps, M=M, D=D)
+        # out = x2 + gamma2 * mlp(l2)
+        Dh = mlp.fc1.out_features
+        pre = new(M, Dh) if save else None
+        hid = new(M, Dh)
+        ops.gemm(l2, pk.w(mlp.fc1.weight), hid, epilogue=EPI_BIAS_GELU, bias=pk.f32(mlp.fc1.bias), C2=pre,
+                 aux_deriv=T == torch.bfloat16)
+        out, f2 = new(M, D, dtype=f32), new(M, D)
+        ops.gemm(hid, pk.w(mlp.fc2.weight), out, epilogue=EPI_RESIDUAL, bias=pk.f32(mlp.fc2.bias), R=x2, gamma=pk.f32(self.gamma2),
+                 C2=f2)
+        if save:
+            self._saved = (xa, l1, mean1, rstd1, qkv, att, stat, f1, x1, l3, mean3, rstd3, u, lstat, p, x2, l2, mean2, rstd2,
+                           pre, hid, f2, self.training, (B, Hg, Wg))
+        return out.view(B, N, D)
+
+    def _backward(self, dout, need_dx):
+        (xa, l1, mean1, rstd1, qkv, att, stat, f1, x1, l3, mean3, rstd3, u, lstat, p, x2, l2, mean2, rstd2, pre, hid, f2,
+         training, (B, Hg, Wg)) = self._take_saved()
+        M, D = xa.shape
+        H, hd, pk, N = self.num_heads, D // self.num_heads, self._pack, Hg * Wg
+        a_, mlp, lp, dev, f32, T = self.attn, self.mlp, self.local_mp, xa.device, torch.float32, l1.dtype
+        new = lambda *shape, dtype=T: torch.empty(shape, dtype=dtype, device=dev)      # noqa: E731
+        G = dout.float().contiguous().view(M, D)
+        # the MLP branch: out = x2 + gamma2 * f2
+        ops.colsum_mul(G, f2, pk.g(self.gamma2), M=M, N=D)
+        gm = ops.scale_cast(G, new(M, D), pk.f32(self.gamma2), M=M, N=D)
+        ops.colsum(gm, pk.g(mlp.fc2.bias))
+        _gemm_dw(gm, hid, pk.g(mlp.fc2.weight), min_rows=256)
+        dH = new(M, mlp.fc1.out_features)
+        ops.gemm(gm, pk.w(mlp.fc2.weight), dH, b_kmajor=False, epilogue=EPI_DGELU, aux=pre, aux_deriv=T == torch.bfloat16)
+        _gemm_dw(dH, l2, pk.g(mlp.fc1.weight), min_rows=256)
+        ops.colsum(dH, pk.g(mlp.fc1.bias))
+        dl2 = new(M, D)
+        ops.gemm(dH, pk.w(mlp.fc1.weight), dl2, b_kmajor=False)
+        # norm2: G1 = G + LN2bwd(dl2), the gradient of x2, and gp = gamma3 * G1, the gradient entering the LPI
+        G1, gp = new(M, D, dtype=f32), new(M, D)
+        ops.layernorm_bwd(dl2, x2, mean2, rstd2, pk.f32(self.norm2.weight), G, G1, gp, pk.g(self.norm2.weight),
+                          pk.g(self.norm2.bias), gb_scale=pk.f32(self.gamma3), M=M, D=D)
+        ops.colsum_mul(G1, p, pk.g(self.gamma3), M=M, N=D)
+        bn, dl3 = lp.bn, new(M, D)
+        ops.lpi_bwd(l3, u, gp, lstat, pk.f32(lp.conv1.weight), pk.f32(lp.conv1.bias), pk.f32(bn.weight), pk.f32(bn.bias),
+                    pk.f32(lp.conv2.weight), dl3, pk.g(lp.conv1.weight), pk.g(lp.conv1.bias), pk.g(bn.weight), pk.g(bn.bias),
+                    pk.g(lp.conv2.weight), pk.g(lp.conv2.bias), B, Hg, Wg, D, training=training)
+        # norm3: G1 += LN3bwd(dl3), the gradient of x1, and ga = gamma1 * G1, the gradient entering proj
+        ga = new(M, D)
+        ops.layernorm_bwd(dl3, x1, mean3, rstd3, pk.f32(self.norm3.weight), G1, G1, ga, pk.g(self.norm3.weight),
+                          pk.g(self.norm3.bias), gb_scale=pk.f32(self.gamma1), M=M, D=D)
+        ops.colsum_mul(G1, f1, pk.g(self.gamma1), M=M, N=D)
+        ops.colsum(ga, pk.g(a_.proj.bias))
+        _gemm_dw(ga, att, pk.g(a_.proj.weight), min_rows=256)
+        datt = new(M, D)
+        ops.gemm(ga, pk.w(a_.proj.weight), datt, b_kmajor=False)
+        dqkv = new(M, 3 * D)
+        ops.xca_bwd(qkv, datt, pk.f32(a_.temperature).view(H), stat, dqkv, pk.g(a_.temperature).view(H), B, N, H, hd)
+        _gemm_dw(dqkv, l1, pk.g(a_.qkv.weight), min_rows=256)
+        if a_.qkv.bias is not None:
+            ops.colsum(dqkv, pk.g(a_.qkv.bias))
+        dl1 = new(M, D)
+        ops.gemm(dqkv, pk.w(a_.qkv.weight), dl1, b_kmajor=False)
+        # norm1 (its parameter gradients are needed whether or not dx is): dx = G1 + LN1bwd(dl1), in place over G1
+        ops.layernorm_bwd(dl1, xa, mean1, rstd1, pk.f32(self.norm1.weight), G1, G1, None, pk.g(self.norm1.weight),
+                          pk.g(self.norm1.bias), M=M, D=D)
+        return G1.view(B, N, D) if need_dx else None
