@@ -373,7 +373,8 @@ int vitmi_ca_out_bwd(const float* G, const float* gamma2, float* dx2, void* gm, 
 
 /* The middle junction of XCiT's XCABlock (models/xcit.py:290-291), whose second branch ends in the LPI kernel and not in a
  * product: y = x + gamma * b (the LayerScale residual) and l = LayerNorm(y) (the next branch's norm) in one pass, the row
- * held in registers between the two.  Additive to ABI 109.
+ * held in registers between the two (layernorm.hip, in the 8-element form of vitmi_layernorm_fwd).
+ * Additive to ABI 109.
  *   x, y: fp32 [M, D], the residual stream; y may be x (in place).  b, l: `dtype` (bf16 or fp32) [M, D], the branch output
  *   and the normed rows.  gamma, ln_weight, ln_bias fp32 [D].  mean, rstd fp32 [M] (of y; two-pass, fp32).
  *   Everything contiguous, every pointer 16-byte aligned; D a multiple of 8 with 8 <= D <= 2048; M >= 1 (M < 2^31).

@@ -1,4 +1,4 @@
-"""The XCABlock's junction kernel (csrc/xcit_glue.hip: ops.ls_residual_ln_fwd, y = x + gamma * b and l = LayerNorm(y) in one
+"""The XCABlock's junction kernel (csrc/layernorm.hip: ops.ls_residual_ln_fwd, y = x + gamma * b and l = LayerNorm(y) in one
 pass) and the XCABlock module on the GPU.
 
 Metric: max |got - want| / max |want| (xcab_util.rel).  Every check prints its error beside its bound (-s).
@@ -16,7 +16,9 @@ test_lpi_gpu.py / test_convembed_gpu.py), per case and per tensor:
     accumulation the bf16 path also has.
   * the junction kernel alone: b is bf16-representable, so both dtypes see the same operands; only l is rounded on store.
     Its figures are the worst over the M of xcab_util.KERNEL_M at each D.
-  * exact: gamma = 0 gives y bit-equal to x; in place (y is x) gives the bits of out of place; a zero dout gives exactly zero
+  * exact: gamma = 0 gives y bit-equal to x; in place (y is x) gives the bits of out of place; ops.layernorm_fwd on the
+    junction's own y gives the junction's l, mean and rstd (the two kernels are neighbours in layernorm.hip and sum a row
+    in the same order: the junction stays that LayerNorm); a zero dout gives exactly zero
     gradients and a zero dx; two rounds on one module give the same bits; num_batches_tracked.
   * the optimizer step: |p' - (p - lr g_ref)| <= lr * (the gradient's bound) * max |g_ref| + 2^-23 max |p| (the fp32 store of p').
 Measured on an MI355X (one run; DESIGN.md 4.9 has the list).
@@ -253,6 +255,21 @@ def test_kernel_gamma_zero_and_in_place(dtype):
         out, inp = run_kernel(t, dtype), run_kernel(t, dtype, in_place=True)
         for k in U.KERNEL_KEYS:
             assert torch.equal(out[k], inp[k]), f"{k}: in place differs from out of place (M {M}, D {D})"
+
+
+@DTYPES
+@pytest.mark.parametrize("D", U.KERNEL_D)
+def test_kernel_is_the_layernorm_of_its_own_y(D, dtype):
+    """ops.layernorm_fwd (ln_fwd8_kernel: y and every vector are 16-byte aligned) on the junction's y, with the same weight,
+    bias and eps, gives the junction's l, mean and rstd bit for bit"""
+    for M in U.KERNEL_M:
+        t = U.kernel_inputs(M, D)
+        got = run_kernel(t, dtype)
+        l = torch.empty((M, D), dtype=dtype, device="cuda")
+        mean, rstd = torch.empty(M, device="cuda"), torch.empty(M, device="cuda")
+        ops.layernorm_fwd(got["y"], t["w"].cuda(), t["bias"].cuda(), l, mean, rstd, U.EPS, M=M, D=D)
+        for k, v in (("l", l), ("mean", mean), ("rstd", rstd)):
+            assert torch.equal(got[k], v), f"{k}: the junction and layernorm_fwd differ (M {M}, D {D})"
 
 
 def test_kernel_refusals():

@@ -1,8 +1,8 @@
 """Float64 restatement of XCiT's XCABlock (the reference's models/xcit.py:264-292, with its XCA :243-254, Mlp and LPI
 :132-141 inside) for the kernel and module tests, the closed-form forward / backward the module runs, the float32 closed
 form, the float64 emulation with the roundings the "bf16" path declares, and a float64 reference of the junction kernel
-(ops.ls_residual_ln_fwd) alone.  Neither touches the library nor the reference tree; tests/golden/xcab.npz pins it to the
-reference's class.
+(ops.ls_residual_ln_fwd, csrc/layernorm.hip) alone.  Neither touches the library nor the reference tree;
+tests/golden/xcab.npz pins it to the reference's class.
 
     x1 = x + g1 (xca(LN1(x) Wqkv^T + bqkv) Wp^T + bp)
     x2 = x1 + g3 lpi(LN3(x1), H, W)

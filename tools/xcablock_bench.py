@@ -1,11 +1,11 @@
 """XCiT's XCABlock on one MI355X: the library's module in bf16, forward (no_grad) and forward + backward, beside a plain
 PyTorch composition of the reference's models/xcit.py:264-292 written here (bf16 parameters and activations, autograd
-backward) on the same device; and the block's junction kernel alone (ops.ls_residual_ln_fwd: y = x + gamma * b, l =
-LayerNorm(y), 12 bytes per element with a bf16 branch) beside the two passes it replaces, a residual pass (ops.ca_merge_fwd,
-which moves the same 10 bytes per element: fp32 x and bf16 branch in, fp32 out) followed by ops.layernorm_fwd (6 bytes per
-element), with the bytes each must move and the largest difference between the two forms' outputs.  Shape: the trunk of
-xcit_small_12_p16 (B 64, 14 x 14 tokens, dim 384, 8 heads).  20 timed calls after 3, device events around the loop.  No pass /
-fail threshold.
+backward) on the same device; and the block's junction kernel alone (ops.ls_residual_ln_fwd, csrc/layernorm.hip: y = x +
+gamma * b, l = LayerNorm(y), 12 bytes per element with a bf16 branch) beside the two passes it replaces, a residual pass
+(ops.ca_merge_fwd, which moves the same 10 bytes per element: fp32 x and bf16 branch in, fp32 out) followed by
+ops.layernorm_fwd (6 bytes per element), with the bytes each must move and the largest difference between the two forms'
+outputs.  Shape: the trunk of xcit_small_12_p16 (B 64, 14 x 14 tokens, dim 384, 8 heads).  20 timed calls after 3, device
+events around the loop.  No pass / fail threshold.
 
     python tools/xcablock_bench.py        # one JSON line
 

@@ -1023,8 +1023,6 @@ __global__ __launch_bounds__(256) void colsum_mul_partial_kernel(const TX* __res
     }
 }
 
-inline int cm_splits(int64_t M) { int64_t s = (M + 3) / 4; return (int)(s < 512 ? s : 512); }
-
 }  // namespace
 
 static int th_check(int H, int Nk, int ld, const char* who) {
@@ -1178,7 +1176,7 @@ extern "C" int vitmi_class_attn_bwd(const void* q, const void* k, const void* v,
   return vitmi_check_launch("class_attn_bwd_kernel");
 }
 
-extern "C" size_t vitmi_colsum_mul_workspace(int64_t M, int64_t N) { return (size_t)cm_splits(M) * (size_t)N * sizeof(float); }
+extern "C" size_t vitmi_colsum_mul_workspace(int64_t M, int64_t N) { return (size_t)colsum_splits(M) * (size_t)N * sizeof(float); }
 
 extern "C" int vitmi_colsum_mul(const void* x, int x_dtype, int64_t ldx, const void* y, int y_dtype, int64_t ldy,
                                 int64_t M, int64_t N, float* out, void* workspace, size_t workspace_bytes,
@@ -1188,7 +1186,7 @@ extern "C" int vitmi_colsum_mul(const void* x, int x_dtype, int64_t ldx, const v
                 VITMI_E_ALIGN, "colsum_mul: N and leading dimensions must be multiples of 4, pointers 4-element aligned");
   VITMI_REQUIRE(workspace && workspace_bytes >= vitmi_colsum_mul_workspace(M, N), VITMI_E_WORKSPACE, "colsum_mul: workspace too small");
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  const int S = cm_splits(M);
+  const int S = colsum_splits(M);
   float* part = reinterpret_cast<float*>(workspace);
   dim3 grid((unsigned)((N + 255) / 256), (unsigned)S);
 #define CM(TX, TY) hipLaunchKernelGGL((colsum_mul_partial_kernel<TX, TY>), grid, dim3(256), 0, stream, (const TX*)x, ldx, (const TY*)y, ldy, M, N, part)

@@ -43,6 +43,12 @@ static inline bool is_aligned(const void* p, size_t a) {
   return (reinterpret_cast<uintptr_t>(p) % a) == 0;
 }
 static inline size_t dtype_size(int dt) { return dt == VITMI_BF16 ? 2 : 4; }
+// partial rows of a two-level column sum over M rows (colsum, colsum_mul, ca_merge_bwd): wave w of workgroup y sums rows
+// 4 y + w, 4 (y + S) + w, ...; vitmi_reduce_rows folds the S rows
+static inline int colsum_splits(int64_t M) {
+  const int64_t s = (M + 3) / 4;
+  return (int)(s < 512 ? s : 512);
+}
 
 // ---- device helpers ----------------------------------------------------
 __device__ __forceinline__ float to_f32(float v) { return v; }

@@ -244,11 +244,6 @@ __global__ __launch_bounds__(1024) void fold_many_kernel(FoldTable t) {
   if (threadIdx.x < FOLD_COLS && c < N) t.out[i][seg][c] = tot;
 }
 
-inline int colsum_splits(int64_t M) {
-  int64_t s = (M + 3) / 4;
-  return (int)(s < 512 ? s : 512);
-}
-
 // ------------------------------------------------------------------ xent --
 // one wave per sample; K classes strided over lanes
 constexpr float XENT_LSE_SWITCH = 16.f;

@@ -1,9 +1,12 @@
 // LayerNorm forward / backward: one wavefront per row, row held in registers,
 // fp32 statistics, 16-B (fp32) / 8-B (bf16) vector accesses.  HBM-bound:
 // fwd moves (sizeof(X)+sizeof(Y))*D bytes per row, bwd
-// (sizeof(dY)+sizeof(X)+2*sizeof(G)+sizeof(Gb))*D.
+// (sizeof(dY)+sizeof(X)+2*sizeof(G)+sizeof(Gb))*D.  The row kernels of this family live here with their helpers and one
+// dispatch: ln_fwd / ln_bwd (4 elements per lane), ln_fwd8 / ln_bwd8 (8 per lane, several rows per wave) and the XCABlock's
+// junction ls_residual_ln (a LayerScale residual and the LayerNorm that reads it, in ln_fwd8's form).
 #include <atomic>
 #include <initializer_list>
+#include <type_traits>
 #include "common.h"
 
 namespace {
@@ -375,6 +378,87 @@ __global__ __launch_bounds__(256) void ln_bwd8_kernel(const TDY* __restrict__ dy
   }
 }
 
+// The middle junction of XCiT's XCABlock (models/xcit.py:290-291 of the reference), in ln_fwd8_kernel's form:
+// y = x + gamma * b (fp32, b widened), l = LayerNorm(y), mean / rstd of y.  The whole row stays in registers between the add
+// and the norm, so the junction moves x, b in and y, l out once (12 B per element with bf16 b / l) where a residual pass
+// followed by vitmi_layernorm_fwd moves 16 (y is written, then read again).  The statistics are ln_fwd8_kernel's, sum for
+// sum: vitmi_layernorm_fwd on the junction's y gives the junction's l, mean and rstd bit for bit (test_xcablock_gpu.py).
+// Every lane reads and writes its own chunks only, so y may be x, and x and y carry no __restrict__.  A chunk is live where
+// its row is below M and its first column below D (D is a multiple of 8, so a live chunk lies wholly inside its row): only
+// live chunks are loaded or stored.
+template <int LPR, int NV, typename T>
+__global__ __launch_bounds__(256) void ls_residual_ln_kernel(const float* x, const T* __restrict__ b,
+                                                             const float* __restrict__ gamma, const float* __restrict__ lnw,
+                                                             const float* __restrict__ lnb, float* y, T* __restrict__ ln,
+                                                             float* __restrict__ mean_out, float* __restrict__ rstd_out,
+                                                             int64_t M, int D, float eps) {
+  constexpr int RPW = 64 / LPR;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int sub = lane / LPR, l = lane % LPR;
+  const int64_t groups = (M + RPW - 1) / RPW;
+  const float invD = 1.f / (float)D;
+  for (int64_t grp = (int64_t)blockIdx.x * 4 + w; grp < groups; grp += (int64_t)gridDim.x * 4) {
+    const int64_t row = grp * RPW + sub;
+    const bool live = row < M;
+    const int64_t base = row * D;
+    float v[NV][8];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = (i * LPR + l) * 8;
+      float g[8];
+      load8<float>(gamma + min(c, D - 8), g);
+      if (live && c < D) {
+        float bv[8];
+        load8<float>(x + base + c, v[i]);
+        load8<T>(b + base + c, bv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          v[i][j] = fmaf(g[j], bv[j], v[i][j]);
+          s += v[i][j];
+        }
+        store8<float>(y + base + c, v[i]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[i][j] = 0.f;
+      }
+    }
+    const float mean = group_sum<LPR>(s) * invD;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+      if ((i * LPR + l) * 8 < D) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float d = v[i][j] - mean; q += d * d; }
+      }
+    const float rstd = rsqrtf(group_sum<LPR>(q) * invD + eps);
+    if (l == 0 && live) {
+      mean_out[row] = mean;
+      rstd_out[row] = rstd;
+    }
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = (i * LPR + l) * 8;
+      float g[8], bb[8];
+      load8<float>(lnw + min(c, D - 8), g);
+      load8<float>(lnb + min(c, D - 8), bb);
+      if (live && c < D) {
+        float o[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (v[i][j] - mean) * rstd * g[j] + bb[j];
+        store8<T>(ln + base + c, o);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- dispatch ---
+// Every fact is written once: the lane-group table (ln8_cfg / with_ln8_cfg), the 4-element form's chunk counts (ln_nv /
+// with_ln_nv), the dtype combinations built (with_fwd_types / with_bwd_types) and the forward grid (ln_fwd_blocks).  The
+// with_* functions turn a run-time value into compile-time ones and hand them to a generic lambda.
+template <int V> using Int = std::integral_constant<int, V>;
+template <typename T> struct Type { using type = T; };
+
 // (LPR, NV) of the 8-element form for a row of D elements (D % 8 == 0): the narrowest lane group whose NV <= 4 chunks cover it
 struct Ln8Cfg { int lpr, nv; };
 inline Ln8Cfg ln8_cfg(int64_t D) {
@@ -387,9 +471,61 @@ inline Ln8Cfg ln8_cfg(int64_t D) {
   if (D <= 1536) return {64, 3};
   return {64, 4};
 }
+template <typename F> void with_ln8_cfg(Ln8Cfg c, F&& f) {      // f(Int<LPR>, Int<NV>): the eight forms ln8_cfg returns
+  switch (c.lpr * 8 + c.nv) {
+    case 16 * 8 + 1: f(Int<16>{}, Int<1>{}); break;
+    case 16 * 8 + 2: f(Int<16>{}, Int<2>{}); break;
+    case 16 * 8 + 3: f(Int<16>{}, Int<3>{}); break;
+    case 32 * 8 + 2: f(Int<32>{}, Int<2>{}); break;
+    case 32 * 8 + 3: f(Int<32>{}, Int<3>{}); break;
+    case 64 * 8 + 2: f(Int<64>{}, Int<2>{}); break;
+    case 64 * 8 + 3: f(Int<64>{}, Int<3>{}); break;
+    default: f(Int<64>{}, Int<4>{}); break;
+  }
+}
 static std::atomic<int> g_ln8{1};     // diagnostic hook (vitmi_debug_ln8): 0 = the 4-element kernels everywhere
 
 inline int ln_nv(int64_t D) { return D <= 512 ? 2 : D <= 768 ? 3 : D <= 1024 ? 4 : LN_MAXV; }
+template <typename F> void with_ln_nv(int64_t D, F&& f) {       // f(Int<NV>) of the 4-element form
+  switch (ln_nv(D)) {
+    case 2: f(Int<2>{}); break;
+    case 3: f(Int<3>{}); break;
+    case 4: f(Int<4>{}); break;
+    default: f(Int<LN_MAXV>{}); break;
+  }
+}
+
+// the (x, y) dtype pairs the forward kernels are built for: f(Type<TX>, Type<TY>); false where the pair is not built
+template <typename F> bool with_fwd_types(int x, int y, F&& f) {
+  const Type<float> f32;
+  const Type<bf16> b16;
+  if (x == VITMI_F32 && y == VITMI_F32) f(f32, f32);
+  else if (x == VITMI_F32 && y == VITMI_BF16) f(f32, b16);
+  else if (x == VITMI_BF16 && y == VITMI_BF16) f(b16, b16);
+  else if (x == VITMI_BF16 && y == VITMI_F32) f(b16, f32);
+  else return false;
+  return true;
+}
+// the (dy, x, g, gb) combinations the backward kernels are built for: activation dtype (dy, gb) and residual dtype (x, g)
+template <typename F> bool with_bwd_types(int dy, int x, int g, int gb, F&& f) {
+  const Type<float> f32;
+  const Type<bf16> b16;
+  if (dy == VITMI_F32 && x == VITMI_F32 && g == VITMI_F32 && gb == VITMI_F32) f(f32, f32, f32, f32);
+  else if (dy == VITMI_BF16 && x == VITMI_F32 && g == VITMI_F32 && gb == VITMI_BF16) f(b16, f32, f32, b16);
+  else if (dy == VITMI_BF16 && x == VITMI_BF16 && g == VITMI_BF16 && gb == VITMI_BF16) f(b16, b16, b16, b16);
+  else if (dy == VITMI_F32 && x == VITMI_BF16 && g == VITMI_BF16 && gb == VITMI_F32) f(f32, b16, b16, f32);
+  else if (dy == VITMI_F32 && x == VITMI_F32 && g == VITMI_F32 && gb == VITMI_BF16) f(f32, f32, f32, b16);
+  else if (dy == VITMI_F32 && x == VITMI_BF16 && g == VITMI_BF16 && gb == VITMI_BF16) f(f32, b16, b16, b16);
+  else return false;
+  return true;
+}
+
+// grid-stride blocks of a forward kernel whose waves take rpw rows at a time (4-element form: 1): 8 blocks per CU keep the
+// loads of several rows in flight per SIMD without paying a workgroup launch per 4 * rpw rows
+inline unsigned ln_fwd_blocks(int64_t M, int rpw) {
+  const int64_t nb = ((M + rpw - 1) / rpw + 3) / 4;
+  return (unsigned)(nb < 2048 ? nb : 2048);
+}
 // grid-stride blocks of the backward kernel: 4 per CU while the row fits few registers
 inline int ln_bwd_blocks(int64_t M, int64_t D) {
   // resident blocks per CU by the kernels' register counts (102 / 132 / 162 / 256+ VGPRs)
@@ -435,61 +571,19 @@ extern "C" int vitmi_layernorm_fwd(const void* x, int x_dtype, int64_t x_stride,
   VITMI_REQUIRE(y_stride % 4 == 0 && is_aligned(y, 4 * dtype_size(y_dtype)) && is_aligned(gamma, 16) && is_aligned(beta, 16),
                 VITMI_E_ALIGN, "layernorm_fwd: y/gamma/beta alignment");
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  if (ln8_ok(D, {x_stride, y_stride}, {x, y, gamma, beta})) {
-    const Ln8Cfg c = ln8_cfg(D);
-    const int rpw = 64 / c.lpr;
-    int64_t nb = ((M + rpw - 1) / rpw + 3) / 4;
-    if (nb > 2048) nb = 2048;
-#define LN_FWD8_T(L, N, TX, TY)                                                                                  \
-    hipLaunchKernelGGL((ln_fwd8_kernel<L, N, TX, TY>), dim3((unsigned)nb), dim3(256), 0, stream, (const TX*)x, x_stride, \
-                       gamma, beta, (TY*)y, y_stride, mean, rstd, M, (int)D, eps)
-#define LN_FWD8(TX, TY)                                                                  \
-    do {                                                                                  \
-      switch (c.lpr * 8 + c.nv) {                                                         \
-        case 16 * 8 + 1: LN_FWD8_T(16, 1, TX, TY); break;                                 \
-        case 16 * 8 + 2: LN_FWD8_T(16, 2, TX, TY); break;                                 \
-        case 16 * 8 + 3: LN_FWD8_T(16, 3, TX, TY); break;                                 \
-        case 32 * 8 + 2: LN_FWD8_T(32, 2, TX, TY); break;                                 \
-        case 32 * 8 + 3: LN_FWD8_T(32, 3, TX, TY); break;                                 \
-        case 64 * 8 + 2: LN_FWD8_T(64, 2, TX, TY); break;                                 \
-        case 64 * 8 + 3: LN_FWD8_T(64, 3, TX, TY); break;                                 \
-        default: LN_FWD8_T(64, 4, TX, TY); break;                                         \
-      }                                                                                   \
-    } while (0)
-    if (x_dtype == VITMI_F32 && y_dtype == VITMI_F32) LN_FWD8(float, float);
-    else if (x_dtype == VITMI_F32 && y_dtype == VITMI_BF16) LN_FWD8(float, bf16);
-    else if (x_dtype == VITMI_BF16 && y_dtype == VITMI_BF16) LN_FWD8(bf16, bf16);
-    else if (x_dtype == VITMI_BF16 && y_dtype == VITMI_F32) LN_FWD8(bf16, float);
-    else return vitmi_fail(VITMI_E_DTYPE, "layernorm_fwd: dtype combination");
-#undef LN_FWD8
-#undef LN_FWD8_T
-    return vitmi_check_launch("ln_fwd8_kernel");
-  }
-  // grid-stride over rows: 8 blocks per CU keep the loads of several rows in flight per
-  // SIMD without paying a workgroup launch per 4 rows
-  int64_t nblk = (M + 3) / 4;
-  if (nblk > 2048) nblk = 2048;
-  dim3 grid((unsigned)nblk), block(256);
-#define LN_FWD_NV(NVV, TX, TY)                                                                     \
-  hipLaunchKernelGGL((ln_fwd_kernel<NVV, TX, TY>), grid, block, 0, stream, (const TX*)x, x_stride, \
-                     gamma, beta, (TY*)y, y_stride, mean, rstd, M, (int)D, eps)
-#define LN_FWD(TX, TY)                                                                        \
-  do {                                                                                        \
-    switch (ln_nv(D)) {                                                                       \
-      case 2: LN_FWD_NV(2, TX, TY); break;                                                    \
-      case 3: LN_FWD_NV(3, TX, TY); break;                                                    \
-      case 4: LN_FWD_NV(4, TX, TY); break;                                                    \
-      default: LN_FWD_NV(LN_MAXV, TX, TY); break;                                             \
-    }                                                                                         \
-  } while (0)
-  if (x_dtype == VITMI_F32 && y_dtype == VITMI_F32) LN_FWD(float, float);
-  else if (x_dtype == VITMI_F32 && y_dtype == VITMI_BF16) LN_FWD(float, bf16);
-  else if (x_dtype == VITMI_BF16 && y_dtype == VITMI_BF16) LN_FWD(bf16, bf16);
-  else if (x_dtype == VITMI_BF16 && y_dtype == VITMI_F32) LN_FWD(bf16, float);
-  else return vitmi_fail(VITMI_E_DTYPE, "layernorm_fwd: dtype combination");
-#undef LN_FWD
-#undef LN_FWD_NV
-  return vitmi_check_launch("ln_fwd_kernel");
+  const bool form8 = ln8_ok(D, {x_stride, y_stride}, {x, y, gamma, beta});
+  const bool built = with_fwd_types(x_dtype, y_dtype, [&](auto tx, auto ty) {
+    using TX = typename decltype(tx)::type;
+    using TY = typename decltype(ty)::type;
+    auto launch = [&](auto kernel, int rpw) {
+      hipLaunchKernelGGL(kernel, dim3(ln_fwd_blocks(M, rpw)), dim3(256), 0, stream, (const TX*)x, x_stride, gamma, beta, (TY*)y,
+                         y_stride, mean, rstd, M, (int)D, eps);
+    };
+    if (form8) with_ln8_cfg(ln8_cfg(D), [&](auto lpr, auto nv) { launch(ln_fwd8_kernel<lpr, nv, TX, TY>, 64 / lpr); });
+    else with_ln_nv(D, [&](auto nv) { launch(ln_fwd_kernel<nv, TX, TY>, 1); });
+  });
+  if (!built) return vitmi_fail(VITMI_E_DTYPE, "layernorm_fwd: dtype combination");
+  return vitmi_check_launch(form8 ? "ln_fwd8_kernel" : "ln_fwd_kernel");
 }
 
 extern "C" size_t vitmi_layernorm_bwd_workspace(int64_t M, int64_t D) {
@@ -543,75 +637,64 @@ extern "C" int vitmi_layernorm_bwd_deferred(const void* dy, int dy_dtype, int64_
   VITMI_REQUIRE(is_aligned(workspace, 16), VITMI_E_ALIGN, "layernorm_bwd: workspace alignment");
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   float* part = reinterpret_cast<float*>(workspace);
-  if (ln8_ok(D, {dy_stride, x_stride, g_stride, gb_out ? gb_stride : 0}, {dy, x, g_in, g_out, gb_out, gamma, gb_scale})) {
-    const Ln8Cfg c = ln8_cfg(D);
-    const int nb8 = ln_bwd8_blocks(M, D);
-    const size_t lds8 = (size_t)4 * (64 / c.lpr) * D * sizeof(float);
-    const int gbd8 = gb_out ? gb_dtype : dy_dtype;
-#define LN_BWD8_T(L, N, TDY, TX, TG, TGB)                                                                            \
-    hipLaunchKernelGGL((ln_bwd8_kernel<L, N, TDY, TX, TG, TGB>), dim3(nb8), dim3(256), lds8, stream, (const TDY*)dy,  \
-                       dy_stride, (const TX*)x, x_stride, mean, rstd, gamma, (const TG*)g_in, (TG*)g_out, g_stride,   \
-                       (TGB*)gb_out, gb_stride, part, gsum ? 1 : 0, gb_scale, gb_rowscale,                            \
-                       rows_per_group > 0 ? rows_per_group : 1, M, (int)D)
-#define LN_BWD8(TDY, TX, TG, TGB)                                                              \
-    do {                                                                                        \
-      switch (c.lpr * 8 + c.nv) {                                                               \
-        case 16 * 8 + 1: LN_BWD8_T(16, 1, TDY, TX, TG, TGB); break;                             \
-        case 16 * 8 + 2: LN_BWD8_T(16, 2, TDY, TX, TG, TGB); break;                             \
-        case 16 * 8 + 3: LN_BWD8_T(16, 3, TDY, TX, TG, TGB); break;                             \
-        case 32 * 8 + 2: LN_BWD8_T(32, 2, TDY, TX, TG, TGB); break;                             \
-        case 32 * 8 + 3: LN_BWD8_T(32, 3, TDY, TX, TG, TGB); break;                             \
-        case 64 * 8 + 2: LN_BWD8_T(64, 2, TDY, TX, TG, TGB); break;                             \
-        case 64 * 8 + 3: LN_BWD8_T(64, 3, TDY, TX, TG, TGB); break;                             \
-        default: LN_BWD8_T(64, 4, TDY, TX, TG, TGB); break;                                     \
-      }                                                                                         \
-    } while (0)
-    if (dy_dtype == VITMI_F32 && x_dtype == VITMI_F32 && g_dtype == VITMI_F32 && gbd8 == VITMI_F32) LN_BWD8(float, float, float, float);
-    else if (dy_dtype == VITMI_BF16 && x_dtype == VITMI_F32 && g_dtype == VITMI_F32 && gbd8 == VITMI_BF16) LN_BWD8(bf16, float, float, bf16);
-    else if (dy_dtype == VITMI_BF16 && x_dtype == VITMI_BF16 && g_dtype == VITMI_BF16 && gbd8 == VITMI_BF16) LN_BWD8(bf16, bf16, bf16, bf16);
-    else if (dy_dtype == VITMI_F32 && x_dtype == VITMI_BF16 && g_dtype == VITMI_BF16 && gbd8 == VITMI_F32) LN_BWD8(float, bf16, bf16, float);
-    else if (dy_dtype == VITMI_F32 && x_dtype == VITMI_F32 && g_dtype == VITMI_F32 && gbd8 == VITMI_BF16) LN_BWD8(float, float, float, bf16);
-    else if (dy_dtype == VITMI_F32 && x_dtype == VITMI_BF16 && g_dtype == VITMI_BF16 && gbd8 == VITMI_BF16) LN_BWD8(float, bf16, bf16, bf16);
-    else return vitmi_fail(VITMI_E_DTYPE, "layernorm_bwd: dtype combination (dy=%d x=%d g=%d gb=%d)", dy_dtype, x_dtype, g_dtype, gbd8);
-#undef LN_BWD8
-#undef LN_BWD8_T
-    rc = vitmi_check_launch("ln_bwd8_kernel");
-    if (rc) return rc;
-    ln_fold_desc(fold, part, nb8, D, dgamma, dbeta, gsum);
-    return 0;
-  }
-  const int nblk = ln_bwd_blocks(M, D);
-  const size_t lds = 4 * (size_t)D * sizeof(float);
-  // activation dtype T (dy, gb) and residual dtype R (x, g) combinations built:
-  //   (T,R) = (f32,f32), (bf16,f32), (bf16,bf16)
-#define LN_BWD_NV(NVV, TDY, TX, TG, TGB)                                                       \
-  hipLaunchKernelGGL((ln_bwd_kernel<NVV, TDY, TX, TG, TGB>), dim3(nblk), dim3(256), lds, stream, \
-                     (const TDY*)dy, dy_stride, (const TX*)x, x_stride, mean, rstd, gamma,     \
-                     (const TG*)g_in, (TG*)g_out, g_stride, (TGB*)gb_out, gb_stride, part,     \
-                     gsum ? 1 : 0, gb_scale, gb_rowscale, rows_per_group > 0 ? rows_per_group : 1, M, (int)D)
-#define LN_BWD(TDY, TX, TG, TGB)                                                               \
-  do {                                                                                         \
-    switch (ln_nv(D)) {                                                                        \
-      case 2: LN_BWD_NV(2, TDY, TX, TG, TGB); break;                                           \
-      case 3: LN_BWD_NV(3, TDY, TX, TG, TGB); break;                                           \
-      case 4: LN_BWD_NV(4, TDY, TX, TG, TGB); break;                                           \
-      default: LN_BWD_NV(LN_MAXV, TDY, TX, TG, TGB); break;                                    \
-    }                                                                                          \
-  } while (0)
+  const bool form8 = ln8_ok(D, {dy_stride, x_stride, g_stride, gb_out ? gb_stride : 0}, {dy, x, g_in, g_out, gb_out, gamma, gb_scale});
+  const int nb = form8 ? ln_bwd8_blocks(M, D) : ln_bwd_blocks(M, D);
+  const size_t lds = (size_t)4 * (form8 ? 64 / ln8_cfg(D).lpr : 1) * D * sizeof(float);      // red[]: a row per wave and row slot
   const int gbd = gb_out ? gb_dtype : dy_dtype;
-  if (dy_dtype == VITMI_F32 && x_dtype == VITMI_F32 && g_dtype == VITMI_F32 && gbd == VITMI_F32) LN_BWD(float, float, float, float);
-  else if (dy_dtype == VITMI_BF16 && x_dtype == VITMI_F32 && g_dtype == VITMI_F32 && gbd == VITMI_BF16) LN_BWD(bf16, float, float, bf16);
-  else if (dy_dtype == VITMI_BF16 && x_dtype == VITMI_BF16 && g_dtype == VITMI_BF16 && gbd == VITMI_BF16) LN_BWD(bf16, bf16, bf16, bf16);
-  else if (dy_dtype == VITMI_F32 && x_dtype == VITMI_BF16 && g_dtype == VITMI_BF16 && gbd == VITMI_F32) LN_BWD(float, bf16, bf16, float);
-  else if (dy_dtype == VITMI_F32 && x_dtype == VITMI_F32 && g_dtype == VITMI_F32 && gbd == VITMI_BF16) LN_BWD(float, float, float, bf16);
-  else if (dy_dtype == VITMI_F32 && x_dtype == VITMI_BF16 && g_dtype == VITMI_BF16 && gbd == VITMI_BF16) LN_BWD(float, bf16, bf16, bf16);
-  else return vitmi_fail(VITMI_E_DTYPE, "layernorm_bwd: dtype combination (dy=%d x=%d g=%d gb=%d)", dy_dtype, x_dtype, g_dtype, gbd);
-#undef LN_BWD
-#undef LN_BWD_NV
-  rc = vitmi_check_launch("ln_bwd_kernel");
+  const bool built = with_bwd_types(dy_dtype, x_dtype, g_dtype, gbd, [&](auto tdy, auto tx, auto tg, auto tgb) {
+    using TDY = typename decltype(tdy)::type;
+    using TX = typename decltype(tx)::type;
+    using TG = typename decltype(tg)::type;
+    using TGB = typename decltype(tgb)::type;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), lds, stream, (const TDY*)dy, dy_stride, (const TX*)x, x_stride, mean, rstd,
+                         gamma, (const TG*)g_in, (TG*)g_out, g_stride, (TGB*)gb_out, gb_stride, part, gsum ? 1 : 0, gb_scale,
+                         gb_rowscale, rows_per_group > 0 ? rows_per_group : 1, M, (int)D);
+    };
+    if (form8) with_ln8_cfg(ln8_cfg(D), [&](auto lpr, auto nv) { launch(ln_bwd8_kernel<lpr, nv, TDY, TX, TG, TGB>); });
+    else with_ln_nv(D, [&](auto nv) { launch(ln_bwd_kernel<nv, TDY, TX, TG, TGB>); });
+  });
+  if (!built)
+    return vitmi_fail(VITMI_E_DTYPE, "layernorm_bwd: dtype combination (dy=%d x=%d g=%d gb=%d)", dy_dtype, x_dtype, g_dtype, gbd);
+  rc = vitmi_check_launch(form8 ? "ln_bwd8_kernel" : "ln_bwd_kernel");
   if (rc) return rc;
-  ln_fold_desc(fold, part, nblk, D, dgamma, dbeta, gsum);
+  ln_fold_desc(fold, part, nb, D, dgamma, dbeta, gsum);
   return 0;
+}
+
+// y = x + gamma * b, l = LayerNorm(y) (ls_residual_ln_kernel).  The 8-element form only: what ln8_ok asks of vitmi_layernorm_fwd
+// (D a multiple of 8, every pointer 16-byte aligned; the rows are contiguous) is a condition here, with no 4-element
+// fallback, and vitmi_debug_ln8 does not apply.
+static bool lsln_dtype_ok(int dtype) { return dtype == VITMI_BF16 || dtype == VITMI_F32; }
+static bool lsln_shape_ok(int64_t M, int64_t D) { return M >= 1 && M < (1ll << 31) && D >= 8 && D % 8 == 0 && D <= LN_MAXV * 256; }
+
+extern "C" int vitmi_ls_residual_ln_supported(int dtype, int64_t M, int64_t D) { return lsln_dtype_ok(dtype) && lsln_shape_ok(M, D); }
+
+extern "C" int vitmi_ls_residual_ln_fwd(const float* x, const void* b, const float* gamma, const float* ln_weight,
+                                        const float* ln_bias, float* y, void* l, float* mean, float* rstd, int dtype, int64_t M,
+                                        int64_t D, float eps, void* stream) {
+  VITMI_REQUIRE(lsln_dtype_ok(dtype), VITMI_E_DTYPE, "ls_residual_ln_fwd: b and l must be bf16 or fp32");
+  VITMI_REQUIRE(lsln_shape_ok(M, D), VITMI_E_SHAPE,
+                "ls_residual_ln_fwd: M = %lld, D = %lld: M >= 1 (below 2^31), D a multiple of 8 with 8 <= D <= %d", (long long)M,
+                (long long)D, LN_MAXV * 256);
+  VITMI_REQUIRE(x && b && gamma && ln_weight && ln_bias && y && l && mean && rstd, VITMI_E_BADARG,
+                "ls_residual_ln_fwd: null pointer");
+  VITMI_REQUIRE(is_aligned(x, 16) && is_aligned(b, 16) && is_aligned(gamma, 16) && is_aligned(ln_weight, 16) &&
+                    is_aligned(ln_bias, 16) && is_aligned(y, 16) && is_aligned(l, 16) && is_aligned(mean, 16) &&
+                    is_aligned(rstd, 16),
+                VITMI_E_ALIGN, "ls_residual_ln_fwd: every pointer must be 16-B aligned");
+  VITMI_REQUIRE(eps >= 0.f, VITMI_E_BADARG, "ls_residual_ln_fwd: eps must not be negative");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  auto launch = [&](auto t) {
+    using T = typename decltype(t)::type;
+    with_ln8_cfg(ln8_cfg(D), [&](auto lpr, auto nv) {
+      hipLaunchKernelGGL((ls_residual_ln_kernel<lpr, nv, T>), dim3(ln_fwd_blocks(M, 64 / lpr)), dim3(256), 0, s, x, (const T*)b,
+                         gamma, ln_weight, ln_bias, y, (T*)l, mean, rstd, M, (int)D, eps);
+    });
+  };
+  if (dtype == VITMI_BF16) launch(Type<bf16>{});
+  else launch(Type<float>{});
+  return vitmi_check_launch("ls_residual_ln_kernel");
 }
 
 // every diagnostic switch of this file back to its default (vitmi_debug_reset, core.cpp)

@@ -25,14 +25,7 @@
 //                               the CLS row is normed); xp: the tensor that holds the patch rows (norm2's output, or x1).
 //   vitmi_ca_out_bwd            dx2[b, n, :] = n == 0 ? G[b, 0, :] : 2 * G[b, n, :];  gm[b, :] = gamma2 * G[b, 0, :] (operand dtype)
 //
-// The middle junction of the XCABlock (models/xcit.py:290-291), a row kernel in the form of layernorm.hip's ln_fwd8_kernel:
-//   vitmi_ls_residual_ln_fwd    y = x + gamma * b (fp32, b widened), l = LayerNorm(y), mean / rstd of y.  A row is spread over
-//                               LPR = 16 / 32 / 64 lanes by D, 8 consecutive elements per lane chunk, NV chunks per lane: the
-//                               whole row stays in registers between the add and the norm, so the junction moves x, b in and
-//                               y, l out once (12 B per element with bf16 b / l) where a residual pass followed by
-//                               vitmi_layernorm_fwd moves 16 (y is written, then read again).  Two-pass mean / variance in
-//                               fp32 by xor-shuffles inside the row's lanes; no LDS, no workspace, no atomics.  Every lane
-//                               reads and writes its own chunks only, so y may be x.
+// The XCABlock's junction (vitmi_ls_residual_ln_fwd) is a LayerNorm row kernel and lives in layernorm.hip.
 #include "common.h"
 
 namespace {
@@ -200,105 +193,6 @@ __global__ __launch_bounds__(NT) void ca_out_bwd_kernel(const float* __restrict_
   }
 }
 
-// ------------------------------------------------------------------------- LayerScale residual + LayerNorm ---
-// (the 8-element loads / stores, the lane-group sum and row_cfg's table below are layernorm.hip's, which keeps them local
-// to its own file)
-__device__ __forceinline__ void load8f(const float* p, float (&o)[8]) {
-  const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-  o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3]; o[4] = b[0]; o[5] = b[1]; o[6] = b[2]; o[7] = b[3];
-}
-template <typename T> __device__ __forceinline__ void load8(const T* p, float (&o)[8]);
-template <> __device__ __forceinline__ void load8<float>(const float* p, float (&o)[8]) { load8f(p, o); }
-template <> __device__ __forceinline__ void load8<bf16>(const bf16* p, float (&o)[8]) {
-  const bf16x8 v = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = (float)v[i];
-}
-template <typename T> __device__ __forceinline__ void store8(T* p, const float (&v)[8]);
-template <> __device__ __forceinline__ void store8<float>(float* p, const float (&v)[8]) {
-  *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-  *reinterpret_cast<f32x4*>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-}
-template <> __device__ __forceinline__ void store8<bf16>(bf16* p, const float (&v)[8]) {
-  bf16x8 o;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = (bf16)v[i];
-  *reinterpret_cast<bf16x8*>(p) = o;
-}
-template <int LPR> __device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = LPR / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// x and y carry no __restrict__: they may be the same tensor.  A chunk is live where its row is below M and its first
-// column below D (D is a multiple of 8, so a live chunk lies wholly inside its row): only live chunks are loaded or stored.
-template <int LPR, int NV, typename T>
-__global__ __launch_bounds__(256) void ls_residual_ln_kernel(const float* x, const T* __restrict__ b,
-                                                             const float* __restrict__ gamma, const float* __restrict__ lnw,
-                                                             const float* __restrict__ lnb, float* y, T* __restrict__ ln,
-                                                             float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                             int64_t M, int D, float eps) {
-  constexpr int RPW = 64 / LPR;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int sub = lane / LPR, l = lane % LPR;
-  const int64_t groups = (M + RPW - 1) / RPW;
-  const float invD = 1.f / (float)D;
-  for (int64_t grp = (int64_t)blockIdx.x * 4 + w; grp < groups; grp += (int64_t)gridDim.x * 4) {
-    const int64_t row = grp * RPW + sub;
-    const bool live = row < M;
-    const int64_t base = row * D;
-    float v[NV][8];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * LPR + l) * 8;
-      float g[8];
-      load8f(gamma + min(c, D - 8), g);
-      if (live && c < D) {
-        float bv[8];
-        load8f(x + base + c, v[i]);
-        load8<T>(b + base + c, bv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          v[i][j] = fmaf(g[j], bv[j], v[i][j]);
-          s += v[i][j];
-        }
-        store8<float>(y + base + c, v[i]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[i][j] = 0.f;
-      }
-    }
-    const float mean = group_sum<LPR>(s) * invD;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-      if ((i * LPR + l) * 8 < D) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const float d = v[i][j] - mean; q += d * d; }
-      }
-    const float rstd = rsqrtf(group_sum<LPR>(q) * invD + eps);
-    if (l == 0 && live) {
-      mean_out[row] = mean;
-      rstd_out[row] = rstd;
-    }
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int c = (i * LPR + l) * 8;
-      float g[8], bb[8];
-      load8f(lnw + min(c, D - 8), g);
-      load8f(lnb + min(c, D - 8), bb);
-      if (live && c < D) {
-        float o[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (v[i][j] - mean) * rstd * g[j] + bb[j];
-        store8<T>(ln + base + c, o);
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------- dispatch ---
 bool dtype_ok(int dtype) { return dtype == VITMI_BF16 || dtype == VITMI_F32; }
 
@@ -325,47 +219,6 @@ unsigned stride_grid(int64_t units) {
   const int64_t blocks = (units + NT - 1) / NT;
   return (unsigned)(blocks < 1 ? 1 : blocks < GRID_CAP ? blocks : GRID_CAP);
 }
-
-constexpr int LSLN_MAX_D = 2048;
-bool lsln_shape_ok(int64_t M, int64_t D) { return M >= 1 && M < (1ll << 31) && D >= 8 && D % 8 == 0 && D <= LSLN_MAX_D; }
-
-// lanes per row and chunks per lane by D: LPR * NV * 8 >= D
-struct RowCfg { int lpr, nv; };
-RowCfg row_cfg(int64_t D) {
-  if (D <= 128) return {16, 1};
-  if (D <= 256) return {16, 2};
-  if (D <= 384) return {16, 3};
-  if (D <= 512) return {32, 2};
-  if (D <= 768) return {32, 3};
-  if (D <= 1024) return {64, 2};
-  if (D <= 1536) return {64, 3};
-  return {64, 4};
-}
-
-template <typename T>
-void lsln_launch(const float* x, const void* b, const float* gamma, const float* lnw, const float* lnb, float* y, void* l,
-                 float* mean, float* rstd, int64_t M, int64_t D, float eps, hipStream_t s) {
-  const RowCfg c = row_cfg(D);
-  const int rpw = 64 / c.lpr;
-  int64_t nb = ((M + rpw - 1) / rpw + 3) / 4;
-  if (nb > 2048) nb = 2048;
-#define LSLN(L, N)                                                                                                          \
-  hipLaunchKernelGGL((ls_residual_ln_kernel<L, N, T>), dim3((unsigned)nb), dim3(256), 0, s, x, (const T*)b, gamma, lnw, lnb, y, \
-                     (T*)l, mean, rstd, M, (int)D, eps)
-  switch (c.lpr * 8 + c.nv) {
-    case 16 * 8 + 1: LSLN(16, 1); break;
-    case 16 * 8 + 2: LSLN(16, 2); break;
-    case 16 * 8 + 3: LSLN(16, 3); break;
-    case 32 * 8 + 2: LSLN(32, 2); break;
-    case 32 * 8 + 3: LSLN(32, 3); break;
-    case 64 * 8 + 2: LSLN(64, 2); break;
-    case 64 * 8 + 3: LSLN(64, 3); break;
-    default: LSLN(64, 4); break;
-  }
-#undef LSLN
-}
-
-int ca_splits(int64_t R) { const int64_t s = (R + 3) / 4; return (int)(s < 512 ? s : 512); }
 
 }  // namespace
 
@@ -439,7 +292,7 @@ extern "C" int vitmi_ca_merge_fwd(const float* x, const void* a, const void* l, 
 
 extern "C" size_t vitmi_ca_merge_bwd_workspace(int64_t B, int64_t N1, int64_t D) {
   if (!ca_shape_ok(B, N1, D)) return 0;
-  return (size_t)ca_splits(B * N1) * (size_t)D * sizeof(float);
+  return (size_t)colsum_splits(B * N1) * (size_t)D * sizeof(float);
 }
 
 extern "C" int vitmi_ca_merge_bwd(const float* dx1, const void* l, const void* a, const float* gamma1, void* da, float* dl,
@@ -453,7 +306,7 @@ extern "C" int vitmi_ca_merge_bwd(const float* dx1, const void* l, const void* a
   VITMI_REQUIRE(workspace && is_aligned(workspace, 16) && workspace_bytes >= vitmi_ca_merge_bwd_workspace(B, N1, D),
                 VITMI_E_WORKSPACE, "ca_merge_bwd: workspace missing, not 16-B aligned or smaller than vitmi_ca_merge_bwd_workspace");
   const int64_t R = B * N1;
-  const int S = ca_splits(R);
+  const int S = colsum_splits(R);
   float* part = reinterpret_cast<float*>(workspace);
   const dim3 grid((unsigned)((D + 255) / 256), (unsigned)S);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -498,26 +351,4 @@ extern "C" int vitmi_ca_out_bwd(const float* G, const float* gamma2, float* dx2,
   else
     hipLaunchKernelGGL((ca_out_bwd_kernel<float>), grid, dim3(NT), 0, s, G, gamma2, dx2, (float*)gm, d);
   return vitmi_check_launch("ca_out_bwd_kernel");
-}
-
-extern "C" int vitmi_ls_residual_ln_supported(int dtype, int64_t M, int64_t D) { return dtype_ok(dtype) && lsln_shape_ok(M, D); }
-
-extern "C" int vitmi_ls_residual_ln_fwd(const float* x, const void* b, const float* gamma, const float* ln_weight,
-                                        const float* ln_bias, float* y, void* l, float* mean, float* rstd, int dtype, int64_t M,
-                                        int64_t D, float eps, void* stream) {
-  VITMI_REQUIRE(dtype_ok(dtype), VITMI_E_DTYPE, "ls_residual_ln_fwd: b and l must be bf16 or fp32");
-  VITMI_REQUIRE(lsln_shape_ok(M, D), VITMI_E_SHAPE,
-                "ls_residual_ln_fwd: M = %lld, D = %lld: M >= 1 (below 2^31), D a multiple of 8 with 8 <= D <= %d", (long long)M,
-                (long long)D, LSLN_MAX_D);
-  VITMI_REQUIRE(x && b && gamma && ln_weight && ln_bias && y && l && mean && rstd, VITMI_E_BADARG,
-                "ls_residual_ln_fwd: null pointer");
-  VITMI_REQUIRE(is_aligned(x, 16) && is_aligned(b, 16) && is_aligned(gamma, 16) && is_aligned(ln_weight, 16) &&
-                    is_aligned(ln_bias, 16) && is_aligned(y, 16) && is_aligned(l, 16) && is_aligned(mean, 16) &&
-                    is_aligned(rstd, 16),
-                VITMI_E_ALIGN, "ls_residual_ln_fwd: every pointer must be 16-B aligned");
-  VITMI_REQUIRE(eps >= 0.f, VITMI_E_BADARG, "ls_residual_ln_fwd: eps must not be negative");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == VITMI_BF16) lsln_launch<bf16>(x, b, gamma, ln_weight, ln_bias, y, l, mean, rstd, M, D, eps, s);
-  else lsln_launch<float>(x, b, gamma, ln_weight, ln_bias, y, l, mean, rstd, M, D, eps, s);
-  return vitmi_check_launch("ls_residual_ln_kernel");
 }

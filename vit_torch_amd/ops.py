@@ -708,8 +708,8 @@ def ls_residual_ln_supported(t, M, D) -> bool:
 
 
 def ls_residual_ln_fwd(x, b, gamma, ln_weight, ln_bias, y, l, mean, rstd, eps, *, M=None, D=None):
-    """y = x + gamma * b and l = LayerNorm(y) in one pass (vitmi_ls_residual_ln_fwd): the junction of a LayerScale residual
-    branch that does not end in a GEMM and the norm that reads the sum.  x, y fp32 [M, D] (y may be x); b, l [M, D] in one
+    """y = x + gamma * b and l = LayerNorm(y) in one pass (vitmi_ls_residual_ln_fwd, layernorm.hip): the junction of a LayerScale
+    residual branch that does not end in a GEMM and the norm that reads the sum.  x, y fp32 [M, D] (y may be x); b, l [M, D] in one
     dtype, bf16 or fp32; gamma, ln_weight, ln_bias fp32 [D]; mean, rstd fp32 [M], of y."""
     _need_cuda(x, b, gamma, ln_weight, ln_bias, y, l, mean, rstd)
     D = D or x.shape[-1]

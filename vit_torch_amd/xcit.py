@@ -37,7 +37,7 @@ State-dict keys are the reference's (`norm1.*`, `attn.qkv.*`, `attn.proj.*`, `no
 local_mp(norm3(x), H, W)`, `x + gamma2 * mlp(norm2(x))`.  One module with one pack on the XCA and LPI kernels (it does not nest
 the `XCA` and `LPI` modules), LayerNorm and the GEMMs: the attention and MLP branches end in a Linear, so the product's
 `EPI_RESIDUAL` epilogue does their LayerScale residual; the LPI branch ends in no product, and its residual and the norm2 that
-reads the sum are one kernel (`ops.ls_residual_ln_fwd`, `xcit_glue.hip`).  The backward uses existing ops only.  State-dict
+reads the sum are one kernel (`ops.ls_residual_ln_fwd`, `layernorm.hip`).  The backward uses existing ops only.  State-dict
 keys, shapes and order are the reference's (`gamma1`, `gamma2`, `gamma3`, `norm1.*`, `attn.temperature`, `attn.qkv.*`,
 `attn.proj.*`, `norm2.*`, `mlp.fc1.*`, `mlp.fc2.*`, `norm3.*`, `local_mp.conv1.*`, `local_mp.bn.*` with the three running
 buffers, `local_mp.conv2.*`).
