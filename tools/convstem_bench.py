@@ -46,10 +46,10 @@ def composed(E, patch):
 
 def per_kernel(m, x):
     """us of each kernel family over the stages, on the tensors of one forward (bf16, training mode)"""
-    from vit_torch_amd import ops
+    from vit_torch_amd import ops, xcit
     bf, pk = torch.bfloat16, m.pack
     t = dict(gather_fwd=0.0, gemm_fwd=0.0, bn_act_fwd=0.0, bn_act_bwd=0.0, gather_bwd=0.0, gemm_dw=0.0, gemm_dcol=0.0, col2im=0.0)
-    stages, B, (h, w), cur = m._stages(), x.shape[0], x.shape[2:], x
+    stages, B, (h, w), cur = xcit._conv_stages(m), x.shape[0], x.shape[2:], x
     for s, (conv, bn) in enumerate(stages):
         co, ci = conv.weight.shape[:2]
         ho, wo = (h + 1) // 2, (w + 1) // 2
@@ -57,7 +57,7 @@ def per_kernel(m, x):
         col, y, out = (torch.empty(sh, dtype=bf, device="cuda") for sh in ((M, K), (M, co), (B, ho * wo, co)))
         dy, dout = torch.empty_like(y), torch.randn((M, co), device="cuda").to(bf)
         stat = torch.empty((2, co), dtype=torch.float32, device="cuda")
-        wk = m._weight(conv, s)
+        wk = xcit._conv_weight(pk, conv, s)
         g = t["gather_fwd"]
         t["gather_fwd"] += _time(lambda: ops.conv3s2_im2col(cur, col, B, h, w, ci))
         t["gather_bwd"] += t["gather_fwd"] - g                      # the backward rebuilds col with the same call

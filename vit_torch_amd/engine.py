@@ -6,8 +6,8 @@ flag lookup (`reducer_flags`) and the one event bracket (`profiled_launch`), the
 parameter pack, gradient bookkeeping), the MLP half-block of a transformer block (`mlp_forward` / `mlp_backward`), the
 autograd bridge (`_EngineFn`) and the `EngineModel` mixin that gives the model classes their `engine()` / `forward()`.
 
-The modules that run without an engine (head.ClassifierHead, xcit.XCA, xcit.LPI) share the `PackedModule` mixin and its
-one autograd bridge (`_PackedFn`) at the end of this file.
+The modules that run without an engine (head.ClassifierHead and xcit's XCA, LPI, ConvPatchEmbed, PositionalEncodingFourier,
+ClassAttentionBlock, XCABlock) share the `PackedModule` mixin and its one autograd bridge (`_PackedFn`) at the end of this file.
 """
 from __future__ import annotations
 
@@ -339,17 +339,19 @@ class _PackedFn(torch.autograd.Function):
 
 
 class PackedModule:
-    """Mixin of an nn.Module that runs on libvitmi kernels by itself (ClassifierHead, XCA, LPI), not inside a model's
+    """Mixin of an nn.Module that runs on libvitmi kernels by itself (ClassifierHead, xcit's modules), not inside a model's
     Engine: its parameters live in a ParamPack (the fused optimizers update them) and one autograd.Function carries
     its forward and backward.  It holds plain attributes only: nothing enters a state_dict, and parameter names, order
     and pack layout are the module's own.  A subclass lists it BEFORE its nn.Module base, sets `pack_shadow` where its
     GEMMs read the pack's bf16 weight shadows, checks its input in `forward` (`_refuse_cpu`, its shapes) and ends it with
-    `self._run(x, *extra)`, and writes `_forward(x, *extra, save)`, which keeps what the backward needs in
-    `self._saved` when `save`, and `_backward(dout, need_dx)`, which starts from `self._take_saved()`, writes the
-    parameter gradients into the pack (`self._pack.g(p)`) and returns dL/dx (None when not need_dx)."""
+    `self._run(x, *extra)`, and names its kernels, plain functions over any pack: `kernels = (forward, backward)` with
+    `forward(pack, m, x, *extra, save) -> (out, saved)` and `backward(pack, m, saved, dout, need_dx) -> dL/dx or None`, which
+    writes the parameter gradients into the pack (`pack.g(p)`).  The mixin refreshes the shadow before the forward and keeps
+    `saved` in `self._saved` between the two; a subclass with more to do overrides `_forward` / `_backward`."""
     _pack = None
     _saved = None
     pack_shadow = False
+    kernels = None
 
     def engine(self):
         """(Re)build the flat parameter buffers (after .to(device) / load_state_dict)."""
@@ -374,6 +376,16 @@ class PackedModule:
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._pack.params)):
             return _PackedFn.apply(self, x, extra, *self._pack.params)
         return self._forward(x, *extra, save=False)
+
+    def _forward(self, x, *extra, save):
+        self._pack.refresh_shadow()
+        out, saved = self.kernels[0](self._pack, self, x, *extra, save=save)
+        if save:
+            self._saved = saved
+        return out
+
+    def _backward(self, dout, need_dx):
+        return self.kernels[1](self._pack, self, self._take_saved(), dout, need_dx)
 
     def _take_saved(self):
         return take_saved(self, "_saved")

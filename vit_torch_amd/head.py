@@ -65,6 +65,8 @@ def head_backward(pack, layers, saved, d, need_dx=True):
 
 
 class ClassifierHead(PackedModule, nn.Sequential):
+    kernels = (lambda pack, m, x, save: head_forward(pack, m._layers, x), None)      # the backward: _backward, with the reducer
+
     def __init__(self, *layers):
         super().__init__(*layers)
         self._layers = _head_layers(self)
@@ -77,13 +79,6 @@ class ClassifierHead(PackedModule, nn.Sequential):
         if not self._layers:
             return x
         return self._run(x.float().contiguous())
-
-    # ---- kernels
-    def _forward(self, x, save):
-        out, saved = head_forward(self._pack, self._layers, x)
-        if save:
-            self._saved = saved
-        return out
 
     def _backward(self, dout, need_dx):
         try:
