@@ -590,6 +590,14 @@ int vitmi_resize_ingest_patchify(const void* src_u8_nhwc, void* out, int out_dty
                                  const float* std, int64_t B, int64_t H, int64_t W, int64_t C, int64_t S, int64_t pad,
                                  int64_t fill, int64_t p, int cls_rows, void* stream);
 
+/* What a vitmi_resize_ingest (band_unit = 1) or vitmi_resize_ingest_patchify (band_unit = p) launch of this geometry
+ * would run with: *band_rows = output rows per workgroup (32, halved while the workgroup's LDS does not fit 64 KiB),
+ * *lds_bytes = its dynamic LDS.  Host arithmetic only, no device call; a geometry the launches refuse (taps, C, crop
+ * fit, LDS at the smallest band) is refused here with the same code and text.  Additive to ABI 109. */
+int vitmi_resize_ingest_plan(int64_t H, int64_t W, int64_t C, int64_t Hr, int64_t Wr, int64_t ytaps, int64_t xtaps,
+                             int64_t S, int64_t pad, int64_t fill, int64_t band_unit, int* band_rows,
+                             int64_t* lds_bytes);
+
 /* optim.Adam / optim.AdamW step (utils_network.py:121,124; torch defaults betas (0.9, 0.999),
  * eps 1e-8, AdamW weight_decay 1e-2) over a flat buffer.  state[0] (device, fp32) is the step
  * count: it is advanced by this call BEFORE the update, so a captured HIP graph replays the

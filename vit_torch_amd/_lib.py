@@ -165,6 +165,7 @@ SIGNATURES = {
     "vitmi_resize_ingest_patchify": (C.c_int, [c_vp, c_vp, C.c_int, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp,
                                                c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
                                                c_i64, C.c_int, c_vp]),
+    "vitmi_resize_ingest_plan": (C.c_int, [c_i64] * 11 + [C.POINTER(C.c_int), C.POINTER(c_i64)]),
     "vitmi_adam": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, C.c_int,
                              c_f32, c_vp]),
     "vitmi_adagrad": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp]),

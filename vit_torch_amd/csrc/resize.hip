@@ -245,6 +245,20 @@ int resize_geom(ResizeGeom& g, int64_t H, int64_t W, int64_t C, int64_t Hr, int6
 
 }  // namespace
 
+// Host-only: the band height and LDS bytes resize_geom picks for a launch of this geometry, or its refusal.
+extern "C" int vitmi_resize_ingest_plan(int64_t H, int64_t W, int64_t C, int64_t Hr, int64_t Wr, int64_t ytaps, int64_t xtaps,
+                                        int64_t S, int64_t pad, int64_t fill, int64_t band_unit, int* band_rows,
+                                        int64_t* lds_bytes) {
+  VITMI_REQUIRE(band_rows && lds_bytes && H > 0 && W > 0 && C > 0 && S > 0 && band_unit > 0 && band_unit <= 64,
+                VITMI_E_BADARG, "resize_ingest_plan: bad argument");
+  ResizeGeom g;
+  size_t lds = 0;
+  if (int rc = resize_geom(g, H, W, C, Hr, Wr, ytaps, xtaps, S, pad, fill, (int)band_unit, &lds)) return rc;
+  *band_rows = g.BR;
+  *lds_bytes = (int64_t)lds;
+  return 0;
+}
+
 extern "C" int vitmi_resize_ingest(const void* src_u8_nhwc, float* dst_nchw, const int32_t* ytab, int64_t ytaps, int64_t Hr,
                                    const int32_t* xtab, int64_t xtaps, int64_t Wr, const int32_t* off_y, const int32_t* off_x,
                                    const uint8_t* flip, const float* mean, const float* stdv, int64_t B, int64_t H,

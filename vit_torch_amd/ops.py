@@ -896,6 +896,17 @@ def resize_ingest_patchify(src, out, ytab, xtab, off_y, off_x, flip, mean, std, 
     return out
 
 
+def resize_ingest_plan(H, W, C, Hr, Wr, ytaps, xtaps, S, pad, fill=128, band_unit=1):
+    """(band_rows, lds_bytes) a resize_ingest (band_unit 1) or resize_ingest_patchify (band_unit p) launch of this
+    geometry runs with; raises where the launch would refuse it.  Host arithmetic only: see vitmi_resize_ingest_plan."""
+    ct = _lib.C                                                           # the module's C is the channel count here
+    band_rows, lds_bytes = ct.c_int(0), ct.c_int64(0)
+    check(load().vitmi_resize_ingest_plan(int(H), int(W), int(C), int(Hr), int(Wr), int(ytaps), int(xtaps), int(S), int(pad),
+                                          int(fill), int(band_unit), ct.byref(band_rows), ct.byref(lds_bytes)),
+          "vitmi_resize_ingest_plan")
+    return band_rows.value, lds_bytes.value
+
+
 def adam(p, g, m, v, shadow, state, lr, beta1, beta2, eps, weight_decay, decoupled, grad_scale=1.0):
     _need_cuda(p, g, m, v, state)
     assert p.dtype == g.dtype == m.dtype == v.dtype == state.dtype == torch.float32
