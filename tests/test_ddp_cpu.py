@@ -7,6 +7,7 @@ mean, and that the result equals single-process gradients on the global batch.""
 import os
 import sys
 
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -164,3 +165,82 @@ def test_network_fit_world2_gloo_equals_one_process_on_the_global_batches():
     # the two ranks' local losses differ (they see different halves) while the all-reduced epoch figures agree
     assert res[0]["local_losses"] != res[1]["local_losses"]
     assert res[0]["train"] == res[1]["train"] and res[0]["val"] == res[1]["val"]
+
+
+# ------------------------------------------------------------------ hip_graph with ddp: what a captured step would leave out ---
+class _EngineLikeModel(torch.nn.Sequential):
+    """What Network needs of an engine model, on the CPU: `engine()` with a `.pack` and a `.reducer`."""
+    _eng = None
+
+    def engine(self):
+        if self._eng is None:
+            import types
+            from vit_torch_amd.packing import ParamPack
+            self._eng = types.SimpleNamespace(pack=ParamPack(list(self.named_parameters()), "cpu", shadow=False), reducer=None)
+        return self._eng
+
+
+@pytest.fixture
+def gloo_world_of_one():
+    from ddp_util import free_port
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()))
+    dist.init_process_group("gloo", rank=0, world_size=1)
+    yield {"size": 1, "rank": 0, "force": True}
+    dist.destroy_process_group()
+
+
+def test_network_refuses_hip_graph_with_ddp_and_a_stock_torch_optimizer(gloo_world_of_one):
+    """A captured step is `backward(); optimizer.step()`: the SUM -> mean pass that `_train_step` runs for a stock torch
+    optimizer is not in it, so the optimizer would step on the SUM (the learning rate times the world size)."""
+    from vit_torch_amd.network import Network
+    model = lambda: _EngineLikeModel(torch.nn.Linear(4, 3))
+    with pytest.raises(ValueError, match="stock torch optimizer"):
+        Network(model(), opt="torch_sgd", device="cpu", hip_graph=True, ddp=gloo_world_of_one)
+    net = Network(model(), opt="torch_sgd", device="cpu", hip_graph=False, ddp=gloo_world_of_one)
+    assert net.reducer is not None and net.model.engine().reducer is net.reducer and net._ddp_pack is None
+    Network(model(), opt="torch_sgd", device="cpu", hip_graph=True)          # no ddp: nothing to refuse
+
+
+def test_network_refuses_hip_graph_with_ddp_around_a_generic_module(gloo_world_of_one):
+    """A generic nn.Module's gradients are exchanged by `_train_step` after backward(): a captured step exchanges nothing."""
+    from vit_torch_amd.network import Network
+    model = lambda: torch.nn.Sequential(torch.nn.Linear(4, 3))
+    with pytest.raises(ValueError, match="generic nn.Module"):
+        Network(model(), opt="torch_sgd", device="cpu", hip_graph=True, ddp=gloo_world_of_one)
+    net = Network(model(), opt="torch_sgd", device="cpu", hip_graph=False, ddp=gloo_world_of_one)
+    assert net.reducer is not None and net._ddp_pack is not None
+
+
+# ------------------------------------------------------------------ Network(ddp={..., 'group': g}) on a sub-group ---
+def _state(*modules):
+    return [{k: v.detach().clone() for k, v in m.state_dict().items()} for m in modules]
+
+
+def _subgroup_worker(rank, world):
+    from vit_torch_amd.network import Network
+    g = dist.new_group([1, 2])               # collective over the whole world: rank 0 only creates it
+    if rank == 0:
+        return None
+    torch.manual_seed(10 + rank)             # every rank starts from other values
+    module = torch.nn.Sequential(torch.nn.Linear(6, 5), torch.nn.BatchNorm1d(5), torch.nn.Linear(5, 3))
+    bottom = torch.nn.Sequential(torch.nn.Linear(4, 6), torch.nn.BatchNorm1d(6))
+    with torch.no_grad():                    # also what is initialised to a constant: BatchNorm's weight, bias and buffers
+        for t in list(module.state_dict().values()) + list(bottom.state_dict().values()):
+            t.add_(rank)
+    before = _state(module, bottom)
+    Network(module, opt="torch_sgd", device="cpu", frozen_model_bottom=bottom, ddp={"size": 2, "rank": rank - 1, "group": g})
+    return {"before": before, "after": _state(module, bottom)}
+
+
+def test_network_on_a_sub_group_broadcasts_from_the_groups_first_rank(tmp_path):
+    """Ranks 1 and 2 of three form the data-parallel group: parameters and buffers of the model and of the frozen bottom
+    come from the group's rank 0, which is global rank 1 (torch's `broadcast(src=)` takes the GLOBAL rank)."""
+    from ddp_util import run_ranks
+    _, r1, r2 = run_ranks(_subgroup_worker, 3, (), tmp_path, limit_s=240)
+    for which in (0, 1):                     # the model, the frozen bottom
+        src = r1["before"][which]
+        assert any(k.endswith("running_mean") for k in src) and any(k.endswith("weight") for k in src)
+        for k, v in src.items():
+            assert not torch.equal(r2["before"][which][k], v), f"{k}: the ranks started equal: the case proves nothing"
+            assert torch.equal(r1["after"][which][k], v), f"{k}: the group's first rank did not keep its own values"
+            assert torch.equal(r2["after"][which][k], v), f"{k}: rank 2 does not hold the values of the group's first rank"

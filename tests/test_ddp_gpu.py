@@ -19,17 +19,7 @@ def _free_port():
     return p
 
 
-@pytest.fixture(scope="module")
-def nccl_world_of_one():
-    import torch.distributed as dist
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(_free_port())
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-    yield dist
-    dist.destroy_process_group()
+from ddp_util import nccl_world_of_one  # noqa: E402,F401  (the fixture, shared with test_ddp_engines_gpu.py)
 
 
 def test_bucketed_allreduce_overlapped_with_backward_matches_plain_step(nccl_world_of_one, lib):

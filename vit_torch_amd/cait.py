@@ -314,7 +314,7 @@ class CaitEngine(Engine):
                           gsum=pk.g(last.mlp.fc2.bias) if last is not None else None,
                           gb_scale=pk.f32(last.gamma_2) if last is not None else None,
                           M=B, D=D, dy_stride=D, x_stride=D, g_stride=ldu, gb_stride=D, fold=self.folds)
-        self._ready(m.norm, *([m.head] if self.head else []))
+        self._ready(m.norm, m.head)
         for bi in range(len(cab) - 1, -1, -1):
             blk = cab[bi]
             a, mlp = blk.attn, blk.mlp

@@ -90,6 +90,13 @@ class GradReducer:
         self.timing = False
         self._ev_last = self._ev_done = None
 
+    def rebuilt_over(self, pack) -> "GradReducer":
+        """A reducer of the same kind over another pack (the model rebuilt its engine: network.Network): same group,
+        `force`, bucket size and transport; nothing of this one's bookkeeping is carried over."""
+        red = type(self)(pack, group=self.group, min_bucket_elems=self.min_bucket, force=self.force, transport=self.transport)
+        red.timing = self.timing
+        return red
+
     # called by the engine when the gradients of `params` are final
     def section_ready(self, params) -> None:
         if (self.world == 1 and not self.force) or not params:

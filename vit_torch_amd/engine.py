@@ -234,6 +234,9 @@ class Engine:
         return engine_gemm(self, A, B, C, **k)
 
     def _ready(self, *mods_or_params):
+        """The gradients of these modules / parameters are final: their section of the flat buffer may leave.  Over one
+        backward the sections tile the whole pack: a parameter the engine never writes (the head of a model built with
+        `apply_head=False`) is announced with its neighbours, zeros included, so every rank steps on the same buffer."""
         if self.reducer is None:
             return
         if self.folds is not None:

@@ -152,6 +152,15 @@ class Network:
         self.earlystop_epoch = earlystop_epoch
         self.world, self.rank, self.reducer, self._ddp_pack = 1, 0, None, None
         if ddp is not None:
+            if hip_graph and (int(ddp["size"]) > 1 or ddp.get("force", False)):
+                # a captured step is `loss.backward(); optimizer.step()` and nothing else (graph.GraphedStep): whatever
+                # _train_step does in Python between the two would silently be left out of it
+                if not hasattr(self.model, "engine"):
+                    raise ValueError("hip_graph=True with ddp needs a vit_torch_amd model or ClassifierHead: a generic "
+                                     "nn.Module's gradients are exchanged after backward(), outside the captured step")
+                if opt.startswith("torch_"):
+                    raise ValueError(f"hip_graph=True with ddp needs a fused optimizer: stock torch optimizer `{opt}` has no "
+                                     "grad_scale, and its SUM -> mean pass over the gradients is not part of the captured step")
             self._setup_ddp(ddp)
         self.optimizer = self.optimizer_fns[opt](self.model.parameters(), lr, 1.0 / self.world)
         self._grad_scale_in_optimizer = isinstance(self.optimizer, _FusedFlat)
@@ -175,10 +184,11 @@ class Network:
             raise ValueError(f"ddp={{'size': {self.world}, 'rank': {self.rank}}} does not match the process group "
                              f"(size {dist.get_world_size(group)}, rank {dist.get_rank(group)})")
         self._group = group
+        src = dist.get_global_rank(group, 0) if group is not None else 0      # torch takes the GLOBAL rank of the group's rank 0
         if self.frozen_model_bottom:
             for m in self.frozen_model_bottom:            # frozen backbones: same weights everywhere, no gradients
                 for t in list(m.parameters()) + list(m.buffers()):
-                    dist.broadcast(t.data, src=0, group=group)
+                    dist.broadcast(t.data, src=src, group=group)
         if hasattr(self.model, "engine"):
             eng = self.model.engine()
             self.reducer = GradReducer(eng.pack, group=group, force=bool(ddp.get("force", False)))
@@ -191,7 +201,21 @@ class Network:
             self.reducer = GradReducer(self._ddp_pack, group=group, force=bool(ddp.get("force", False)))
         self.reducer.broadcast_parameters(0)
         for b in self.model.buffers():
-            dist.broadcast(b.data, src=0, group=group)
+            dist.broadcast(b.data, src=src, group=group)
+
+    def _reducer_follows_engine(self):
+        """The reducer sits on an engine INSTANCE over that engine's pack, and `model.engine()` builds a new engine with
+        new flat buffers whenever its configuration moved (`_engine = None` after a checkpoint load, `.to()`, a Swin
+        drop-path edit, another compute_dtype / split3 / cls_only_last_block; a ClassifierHead rebuilds its `_pack`).  The
+        fused optimizer follows the parameters to the new pack with its grad_scale = 1 / world, so a reducer left
+        behind would mean: no bucket leaves, every rank steps on its own gradient / world.  Called before every step:
+        a few attribute comparisons, no launch, no synchronisation.  The new pack copied the current parameter values,
+        which are equal on all ranks already, so nothing is broadcast again."""
+        if self.reducer is None or self._ddp_pack is not None:
+            return
+        eng = self.model.engine()
+        if eng.reducer is not self.reducer or self.reducer.pack is not eng.pack:
+            self.reducer = eng.reducer = self.reducer.rebuilt_over(eng.pack)
 
     def distributed_loader(self, dataset, batch_size, shuffle=False, num_workers=0, seed=0):
         """The reference's hook (utils_datasets.py:876-891): `DistributedSampler(num_replicas=ddp['size'],
@@ -233,6 +257,7 @@ class Network:
     def _train_step(self, inputs, labels):
         """utils_network.py:418-442 for one batch; in a data-parallel job the gradients every rank steps on are the
         global-batch mean."""
+        self._reducer_follows_engine()
         outputs = self.model(inputs)
         loss = self.loss_fn(outputs, labels)
         self.optimizer.zero_grad()
@@ -268,6 +293,7 @@ class Network:
                 g = self._graphed
                 if g is None and inputs.is_cuda:
                     from .graph import GraphedStep
+                    self._reducer_follows_engine()       # GraphedStep reads the reducer off the engine it captures
                     # one eager step on this batch (it counts as the batch's update), then the capture
                     g = self._graphed = GraphedStep(self.model, self.loss_fn, self.optimizer, inputs, labels, warmup=1)
                     outputs, loss = g.warm_out, g.warm_loss

@@ -377,7 +377,7 @@ class SwinEngine(Engine):
         ops.layernorm_bwd(dxn, s["Xf"], s["meanf"], s["rstdf"], pk.f32(m.norm.weight), None, G, Gb,
                           pk.g(m.norm.weight), pk.g(m.norm.bias), gsum=pk.g(last_blk.mlp.fc2.bias),
                           gb_rowscale=s["stages"][-1][0][-1][-1], rows_per_group=L, M=M, D=C, fold=self.folds)
-        self._ready(m.norm, *([m.head] if self.head else []))
+        self._ready(m.norm, m.head)
 
         layers = list(m.layers)
         for li in range(len(layers) - 1, -1, -1):

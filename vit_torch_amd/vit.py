@@ -457,7 +457,7 @@ class VitEngine(Engine):
             ops.layernorm_bwd(dfeat, s["Xf"], s["meanf"], s["rstdf"], pk.f32(m.norm.weight), None, Gc, None,
                               pk.g(m.norm.weight), pk.g(m.norm.bias), M=B, D=D, dy_stride=D, x_stride=D, g_stride=D,
                               fold=self.folds)
-            self._ready(m.norm, *([m.head] if self.head else []))
+            self._ready(m.norm, m.head)
             last = blocks_list.pop()
             prev = blocks_list[-1].mlp.fc2.bias if blocks_list else None
             G, Gb = self._last_block_cls_bwd(last, s["last_cls"], Gc, B, N, M, D, H, hd, dev, prev)
@@ -471,7 +471,7 @@ class VitEngine(Engine):
             ops.layernorm_bwd(dfeat, s["Xf"], s["meanf"], s["rstdf"], pk.f32(m.norm.weight), None, G, None,
                               pk.g(m.norm.weight), pk.g(m.norm.bias), gsum=pk.g(last_fc2_bias), M=B, D=D,
                               dy_stride=D, x_stride=N * D, g_stride=N * D, fold=self.folds)
-            self._ready(m.norm, *([m.head] if self.head else []))
+            self._ready(m.norm, m.head)
             if T == R:
                 Gb = G                      # GEMM operand and residual gradient share one buffer
             else:
