@@ -17,6 +17,8 @@ Paths (gemm_util.PATHS; shapes there):
   t256.padded           VITMI_LAUNCH_ROWS_PADDED: ragged M on the 256x256 tile
   t128                  256x128 tile, whole and ragged shapes and its split-K
   pair, split3          vitmi_gemm_pair (paired and fallen back), ops.gemm_split3
+  batch > 1             tests/test_gemm_batched_gpu.py: gemm_small.hip forms 0 / 1 / 2, its split over workgroups, every
+                        fallback to the generic kernel and the generic kernel under blockIdx.z
 
 Section 3.1 (test_exact_*): the `integer` family; every product, partial sum and epilogue value is an exact integer (or
 half-integer with alpha = 0.5), so C, C2 and colsum_part must be torch.equal to the reference in any summation order.

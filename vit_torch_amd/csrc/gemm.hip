@@ -358,12 +358,13 @@ static int build_args(const vitmi_gemm_desc* d, GemmArgs* out) {
 
 int gemm_small_form(const GemmArgs& g, int in_bf16);
 int gemm_small_launch(const GemmArgs& g, int form, hipStream_t stream);
+int gemm_small_parts(const GemmArgs& g, int form);
 static std::atomic<int> g_small_override{-1};    // diagnostic / test hook: 0 = never, 1 = also when impl == GENERIC, -1 = default
 extern "C" void vitmi_debug_gemm_small(int mode) { g_small_override = mode; }
 static bool small_lds_ok(const GemmArgs& g, int form) {
   if (form == 0) return ((g.N + 15) / 16 * 16) * (64 * 2 + 16) <= 96 * 1024;
-  const int64_t Kp = (g.K + 31) / 32 * 32, Mp = (g.M + 15) / 16 * 16;
-  const int64_t ry = g.N * 2 + (((g.N * 2) % 128 == 0) ? 32 : 0), rs = Mp * 2 + (((Mp * 2) % 128 == 0) ? 32 : 0);
+  const int64_t Kp = (g.K + 31) / 32 * 32, Mp = (g.M + 15) / 16 * 16, Np = (g.N + 15) / 16 * 16;
+  const int64_t ry = Np * 2 + (((Np * 2) % 128 == 0) ? 32 : 0), rs = Mp * 2 + (((Mp * 2) % 128 == 0) ? 32 : 0);
   return Kp * ry + (form == 2 ? 64 * rs : 0) <= 96 * 1024;
 }
 
@@ -407,6 +408,21 @@ extern "C" int vitmi_debug_gemm_plan(const vitmi_gemm_desc* d, int* kind, int* p
   VITMI_REQUIRE(kind && pipe && deep && splits, VITMI_E_BADARG, "gemm_plan: null output");
   *kind = -1; *pipe = *deep = *splits = 0;
   if (choose_path(d, g, &form) == PATH_FAST) gemm_fast_plan_query(g, kind, pipe, deep, splits);
+  return 0;
+}
+
+// diagnostic / test hook: which kernel family vitmi_gemm would launch for this descriptor (build_args + choose_path, the
+// call's own).  path: GemmPath; form: the small / skinny kernel's form (-1 on the other paths); parts: the workgroups per
+// problem gemm_small_launch would use (0 off PATH_SMALL)
+extern "C" int vitmi_debug_gemm_path(const vitmi_gemm_desc* d, int* path, int* form, int* parts) {
+  GemmArgs g;
+  if (int rc = build_args(d, &g)) return rc;
+  VITMI_REQUIRE(path && form && parts, VITMI_E_BADARG, "gemm_path: null output");
+  int f = -1;
+  const GemmPath p = choose_path(d, g, &f);
+  *path = (int)p;
+  *form = (p == PATH_SMALL || p == PATH_SKINNY) ? f : -1;
+  *parts = p == PATH_SMALL ? gemm_small_parts(g, f) : 0;
   return 0;
 }
 

@@ -188,9 +188,13 @@ __global__ __launch_bounds__(256) void gemm_small_kernel(SmallArgs a) {
     }
   } else {
     const int Kp = (K + 31) / 32 * 32;
-    const int RSY = y_pitch(N);
+    // the pitch covers the PADDED row: stage_rows writes Np columns (zeros beyond N) and tr_frag reads 16 per column
+    // tile.  It used to be y_pitch(N): at N % 16 == 8 (N = 8, 24, 40, 56) the zero piece of row k landed on the first
+    // 16 bytes of row k + 1, racing with that row's own data (tests/test_gemm_batched_gpu.py f1.N8 / f2.N8: exact zeros
+    // where the product was not zero).  N % 16 == 0, every head dim the models use, has the same pitch as before.
     const int Np = tiles_n * 16;
-    char* Ys = smem;                               // [Kp][N] row-major, rows >= K zero
+    const int RSY = y_pitch(Np);
+    char* Ys = smem;                               // [Kp][Np] row-major, rows >= K and columns >= N zero
     stage_rows(Ys, RSY, B, a.ldb, 0, Kp, K, N, Np, tid, 256);
     if constexpr (FORM == 1) {
       __syncthreads();
@@ -269,8 +273,8 @@ __global__ __launch_bounds__(256) void gemm_small_kernel(SmallArgs a) {
 
 inline size_t small_lds(int form, int M, int N, int K) {
   if (form == 0) return (size_t)((N + 15) / 16 * 16) * (64 * 2 + 16);
-  const int Kp = (K + 31) / 32 * 32;
-  const int RSY = N * 2 + (((N * 2) % 128 == 0) ? 32 : 0);
+  const int Kp = (K + 31) / 32 * 32, Np = (N + 15) / 16 * 16;
+  const int RSY = Np * 2 + (((Np * 2) % 128 == 0) ? 32 : 0);
   size_t b = (size_t)Kp * RSY;
   if (form == 2) {
     const int Mp = (M + 15) / 16 * 16;
@@ -299,6 +303,16 @@ int gemm_small_form(const GemmArgs& g, int in_bf16) {
   return -1;
 }
 
+// workgroups per problem: the launch's grid.y, and what vitmi_debug_gemm_path (gemm.hip) reports
+// fewer than four workgroups per CU: split the row tiles of a problem over two workgroups
+// (measured at 512 problems of 196 x 196 x 48: form 0 22.3 -> 20.3 us, form 1 22.1 -> 16.7;
+// form 2 streams S through LDS once per workgroup, so a second one doubles that: 24.5 -> 35.9)
+int gemm_small_parts(const GemmArgs& g, int form) {
+  if (g_small_parts > 0) return g_small_parts;
+  const int tiles_m = ((int)g.M + 15) / 16;
+  return (form != 2 && g.batch < 4 * (int64_t)vitmi_cu_count() && tiles_m >= 8) ? 2 : 1;
+}
+
 int gemm_small_launch(const GemmArgs& g, int form, hipStream_t stream) {
   SmallArgs a;
   a.A = reinterpret_cast<const bf16*>(g.A); a.B = reinterpret_cast<const bf16*>(g.B);
@@ -309,14 +323,7 @@ int gemm_small_launch(const GemmArgs& g, int form, hipStream_t stream) {
   for (int i = 0; i < 2; ++i) { a.a_bs[i] = g.a_bs[i]; a.b_bs[i] = g.b_bs[i]; a.c_bs[i] = g.c_bs[i]; }
   a.alpha = g.e.alpha;
   const size_t lds = small_lds(form, a.M, a.N, a.K);
-  // fewer than four workgroups per CU: split the row tiles of a problem over two workgroups
-  const int cus = vitmi_cu_count();
-  const int tiles_m = (a.M + 15) / 16;
-  // (measured at 512 problems of 196 x 196 x 48: form 0 22.3 -> 20.3 us, form 1 22.1 -> 16.7;
-  // form 2 streams S through LDS once per workgroup, so a second one doubles that: 24.5 -> 35.9)
-  const unsigned parts = (g_small_parts > 0) ? (unsigned)g_small_parts
-                         : ((form != 2 && g.batch < 4 * (int64_t)cus && tiles_m >= 8) ? 2u : 1u);
-  const dim3 grid((unsigned)g.batch, parts);
+  const dim3 grid((unsigned)g.batch, (unsigned)gemm_small_parts(g, form));
 #define SMALL_GO(F)                                                                                   \
   do {                                                                                                \
     auto kern = gemm_small_kernel<F>;                                                                 \
